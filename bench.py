@@ -10,6 +10,12 @@ fusion, per-GPU batch 8 clips x 8 frames x 224^2 + 32-token captions, all five l
 MFMA compute with fp32 master weights.  Synthetic data (SURVEY §8d generator, seed 1000+rank),
 random-init weights, inputs resident in HBM before the timed region.  Weak scaling: per-GPU
 batch fixed; `value` = global pairs / max-over-ranks time.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON line.  --full adds what is measured beside
+it: the loss check against the fp32 CPU oracle and the oracle's own speed (`cpu_baseline`, `loss_abs_err_vs_oracle`;
+off with --no-cpu-baseline), per-kernel event timing with the roofline (`roofline`, `kernels`; off with
+--no-kernel-timing) and the step fed from outside the graphs' input buffers (`ms_per_step_with_input_copy`).
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy (dump_outputs()).
 """
 import argparse
 import json
@@ -154,6 +160,41 @@ def cpu_baseline(cfg, state, frames, L, budget_s=25.0):
                        f'{len(times)} {note} ({per:.2f} s/iter)')
 
 
+DUMP_PER_PARAM = 4096           # --dump-outputs: elements sampled per parameter tensor
+
+
+def dump_outputs(path, engine, out, grad_norm):
+    """What the last timed step handed its caller, as .npy files under `path`: the loss and the logged losses
+    (loss.npy, log_<name>.npy: float64 scalars), the global gradient norm, and the parameters after the update with
+    AdamW's two moments (params.npy, exp_avg.npy, exp_avg_sq.npy: float32).  Per parameter, in the order of the names,
+    at most DUMP_PER_PARAM elements at indices drawn from a generator seeded by the parameter's name: the same elements
+    from run to run and from build to build, whatever the layout of the flat slabs."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def scalar(name, v):
+        np.save(os.path.join(path, name + '.npy'), np.array(float(v), dtype=np.float64))
+    scalar('loss', out['loss'])
+    for k, v in out['log_vars'].items():
+        scalar('log_' + k, v)
+    scalar('grad_norm', grad_norm)
+    slots = sorted(((n, seg, off, p.numel()) for seg in engine.segments
+                    for n, p, off in zip(seg.names, seg.params, seg.offsets)), key=lambda t: t[0])
+    picks = dict(params=[], exp_avg=[], exp_avg_sq=[])
+    for name, seg, off, n in slots:
+        if n <= DUMP_PER_PARAM:
+            idx = torch.arange(n)
+        else:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, n, (DUMP_PER_PARAM,), generator=g).sort().values
+        idx = idx.to(seg.flat_p.device) + off
+        for key, flat in (('params', seg.flat_p), ('exp_avg', seg.exp_avg), ('exp_avg_sq', seg.exp_avg_sq)):
+            picks[key].append(flat[idx])
+    for key, parts in picks.items():
+        np.save(os.path.join(path, key + '.npy'), torch.cat(parts).float().cpu().numpy())
+
+
 def cpu_baseline_subprocess(variant, frames, L, timeout_s=240):
     """Run the CPU leg in a child process that never touches the GPU (own thread pool, hard
     timeout) so it cannot stall the GPU process; same seed -> same random-init weights."""
@@ -188,12 +229,22 @@ def main():
                          'reference trains in fp16 (pretrain_webvid_cc3m.py:21); bf16: the same kernels compiled for bf16 '
                          '(libclover_hip.so: same step time, losses 1.8e-2 instead of 2e-3 from the fp32 reference); '
                          'fp8: forward GEMMs on e4m3 operands (BASELINE config 5) over bf16, gradients stay bf16')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the measurements beside the headline figure: CPU oracle baseline + loss check, per-kernel '
+                         'timing + roofline, the step with an input staging copy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: without the CPU oracle leg')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: without the per-kernel timing')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/*.npy (losses, gradient norm, a fixed sample of '
+                         'the updated parameters and AdamW moments)')
     ap.add_argument('--phases', action='store_true', help='after the timed region: GPU time per phase of the graphed step (events at the phase boundaries), as a "phases_ms" field')
     ap.add_argument('--no-graph', action='store_true', help='run the step eagerly instead of as one hipGraph')
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    cpu_leg = args.full and not args.no_cpu_baseline
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if args.cpu_baseline_only:                           # child of cpu_baseline_subprocess(): CPU only
         import clover_amd
@@ -236,7 +287,7 @@ def main():
     # B = 2 batch the oracle is timed on, eval mode (no dropout / DropPath, as the oracle), on the bf16 training path and
     # in parity mode (fp32 storage + arithmetic on the HIP kernels); compared with the oracle's losses below.
     own_losses = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_leg:
         from clover_amd import parity
         cb = {k: v.to(dev) for k, v in synthetic_batch(2, args.frames, args.tokens, seed=999).items()}
         model.eval()
@@ -280,7 +331,7 @@ def main():
     for _ in range(args.warmup):
         out = engine.step(batch)
     sync()
-    if not args.no_kernel_timing and not graphed:
+    if kernel_timing and not graphed:
         ops.PROF = {}
     if engine.reducer.active:
         engine.reducer.start_timing()                    # stall of the compute stream on the gradient all-reduces
@@ -292,17 +343,21 @@ def main():
     dt = time.perf_counter() - t0
     steps_skipped = ops.optim_state_read(engine.optim_state)['skipped'] - skipped0      # overflow-skipped updates in the timed region
     exposed_comm_ms = engine.reducer.exposed_ms() if engine.reducer.active else None
+    log_vars = {k: float(v) for k, v in out['log_vars'].items()}          # the last timed step's
+    gnorm = engine.grad_norm()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, out, gnorm)
     prof, ops.PROF = ops.PROF, None
     prof_steps = args.steps
     with_copy_ms = None
-    if graphed:
+    if graphed and args.full:
         # the same steps fed from tensors OUTSIDE the graphs' static input buffers (what a loader that does not write
         # into engine.input_buffers() pays: one device-to-device staging copy of the batch per step) — ADVICE r2
         fresh = {k: v.clone() for k, v in batch.items()}
         sync()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            out = engine.step(fresh)
+            engine.step(fresh)
         sync()
         with_copy_ms = (time.perf_counter() - t1) / args.steps * 1e3
         del fresh
@@ -313,7 +368,7 @@ def main():
             engine.step(batch)
         sync()
         phases_ms = {k: round(v, 3) for k, v in engine.phase_ms().items()}
-    if graphed and not args.no_kernel_timing:
+    if graphed and kernel_timing:
         # per-kernel durations: HIP events cannot bracket launches inside a replayed graph, so the same
         # kernels (same shapes, same data) are timed on 3 eager steps right after the timed region.  Each
         # eager step is queued behind ~40 ms of filler GEMMs so that the host runs ahead and the step's
@@ -336,8 +391,6 @@ def main():
     if dist.is_initialized():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    log_vars = {k: float(v) for k, v in out['log_vars'].items()}
-    gnorm = engine.grad_norm()
 
     if rank == 0:
         gb = args.batch * world
@@ -444,7 +497,7 @@ def main():
                 counter_fields(res['roofline_2'])
         res['library_gemm_calls'] = {f'{k[0]} {list(k[1])}': v for k, v in ops.LIBRARY_GEMM_CALLS.items()}
         res['library_gemm_calls_setup'] = {f'{k[0]} {list(k[1])}': v for k, v in lib_setup.items()}
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_leg and world == 1:
             res['cpu_baseline'] = cpu_baseline_subprocess(args.variant, args.frames, args.tokens)
             ref = res['cpu_baseline'].pop('losses', None)
             if ref and own_losses:

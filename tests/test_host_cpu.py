@@ -535,3 +535,45 @@ def test_sumsq_range_table_host_logic():
     assert torch.equal(covered, want)
     tab0, n0 = ops.sumsq_range_table([], 'cpu')
     assert n0 == 0
+
+
+def test_bench_dump_outputs_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the losses and the gradient norm as float64 scalars, the parameters and AdamW moments as
+    float32 samples at indices fixed by the parameter names — the same arrays for two slab layouts of the same weights,
+    within the size bound."""
+    from types import SimpleNamespace
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(5)
+    params = {'a.weight': torch.randn(300, 40, generator=g), 'b.bias': torch.randn(24, generator=g),
+              'c.weight': torch.randn(8, 8, generator=g)}
+
+    def engine(order):
+        offs, n = [], 0
+        for name in order:
+            offs.append(n)
+            n += (params[name].numel() + 7) // 8 * 8
+        seg = SimpleNamespace(names=list(order), params=[params[k] for k in order], offsets=offs,
+                              flat_p=torch.zeros(n), exp_avg=torch.zeros(n), exp_avg_sq=torch.zeros(n))
+        for k, off in zip(order, offs):
+            m = params[k].numel()
+            seg.flat_p[off:off + m] = params[k].reshape(-1)
+            seg.exp_avg[off:off + m] = 0.1 * params[k].reshape(-1)
+            seg.exp_avg_sq[off:off + m] = params[k].reshape(-1) ** 2
+        return SimpleNamespace(segments=[seg])
+    out = dict(loss=torch.tensor(3.5), log_vars={'mlm_loss': 1.25, 'loss': 3.5})
+    bench.dump_outputs(str(tmp_path / 'x'), engine(['a.weight', 'b.bias', 'c.weight']), out, 7.0)
+    bench.dump_outputs(str(tmp_path / 'y'), engine(['c.weight', 'a.weight', 'b.bias']), out, 7.0)
+    names = sorted(os.listdir(tmp_path / 'x'))
+    assert names == sorted(os.listdir(tmp_path / 'y')) == sorted(
+        ['loss.npy', 'log_mlm_loss.npy', 'log_loss.npy', 'grad_norm.npy', 'params.npy', 'exp_avg.npy', 'exp_avg_sq.npy'])
+    for f in names:
+        a, b = np.load(tmp_path / 'x' / f), np.load(tmp_path / 'y' / f)
+        assert a.dtype == (np.float32 if f.startswith(('params', 'exp_avg')) else np.float64), f
+        assert np.array_equal(a, b), f
+    assert float(np.load(tmp_path / 'x' / 'log_mlm_loss.npy')) == 1.25 and float(np.load(tmp_path / 'x' / 'grad_norm.npy')) == 7.0
+    p = np.load(tmp_path / 'x' / 'params.npy')
+    assert p.size == min(12000, bench.DUMP_PER_PARAM) + 24 + 64
+    assert np.isin(p[:bench.DUMP_PER_PARAM], params['a.weight'].numpy()).all()          # names in order: a, b, c
+    assert np.array_equal(p[bench.DUMP_PER_PARAM:], torch.cat([params['b.bias'], params['c.weight'].reshape(-1)]).numpy())
+    assert np.allclose(np.load(tmp_path / 'x' / 'exp_avg.npy'), 0.1 * p)

@@ -5,18 +5,19 @@
 # one 16x16x32 bf16 MFMA keeps a SIMD busy 16 cycles (checked: busy = 16 x SQ_INSTS_MFMA), so the ratio is the
 # fraction of the dense bf16 MFMA peak.  ROCm 7.2 ships no derived metrics for gfx950 (MI355X_MICROARCH.md).
 set -u
+OUT=$(realpath -m "${OUT:-out}"); export OUT      # results directory (default: out/)
 export TMPDIR=/tmp
 R=$PWD
-rm -rf $R/gpurun_out/pmc_mfma; mkdir -p $R/gpurun_out/pmc_mfma
+rm -rf $OUT/pmc_mfma; mkdir -p $OUT/pmc_mfma
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE \
-   --output-format csv -d $R/gpurun_out/pmc_mfma -o p -- \
-   python3 $R/bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing ${BENCH_ARGS:-} > $R/gpurun_out/pmc_mfma/stdout.log 2>&1)
+   --output-format csv -d $OUT/pmc_mfma -o p -- \
+   python3 $R/bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing ${BENCH_ARGS:-} > $OUT/pmc_mfma/stdout.log 2>&1)
 echo "rc=$?"
-find gpurun_out/pmc_mfma -name '*kernel_trace.csv' -delete
-python3 - <<'PY' > gpurun_out/pmc_mfma.json
-import csv, glob, json, collections, re
+find $OUT/pmc_mfma -name '*kernel_trace.csv' -delete
+python3 - <<'PY' > $OUT/pmc_mfma.json
+import csv, glob, json, collections, os, re
 acc = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))
-for f in glob.glob('gpurun_out/pmc_mfma/**/*counter_collection.csv', recursive=True):
+for f in glob.glob(os.environ['OUT'] + '/pmc_mfma/**/*counter_collection.csv', recursive=True):
     for r in csv.DictReader(open(f)):
         n = r['Kernel_Name']
         if n.startswith(('Cijk', 'Custom_Cijk')):
@@ -42,5 +43,5 @@ res = dict(sorted(out.items(), key=lambda kv: -kv[1]['gui_active_cycles'] * kv[1
 res['_meta'] = dict(commit=os.environ.get('CLOVER_COMMIT', 'unknown'), csrc_sha16=csrc_sha16(), command='bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing ' + os.environ.get('BENCH_ARGS', ''))
 print(json.dumps(res, indent=1))
 PY
-head -c 1800 gpurun_out/pmc_mfma.json
-find gpurun_out/pmc_mfma -name '*counter_collection.csv' -size +20M -delete
+head -c 1800 $OUT/pmc_mfma.json
+find $OUT/pmc_mfma -name '*counter_collection.csv' -size +20M -delete
