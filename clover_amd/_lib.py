@@ -35,7 +35,7 @@ def half_dtype():
     import torch
     return torch.float16 if HALF_F16 else torch.bfloat16
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 ERRORS = {-1: 'CLV_ERR_ARG (bad argument)', -2: 'CLV_ERR_UNSUPPORTED (shape not supported by the kernels)',
           -3: 'CLV_ERR_LAUNCH (HIP launch failed)'}
@@ -174,6 +174,14 @@ SIGNATURES = {
     'clv_attn_f32_fwd': (C.c_int, [_p] * 7 + [C.POINTER(ClvAttnGeom), _i32, _p]),
     'clv_attn_f32_bwd_work_floats': (C.c_int64, [C.POINTER(ClvAttnGeom)]),
     'clv_attn_f32_bwd': (C.c_int, [_p] * 12 + [C.POINTER(ClvAttnGeom), _p]),
+    'clv_qa_answer_rows': (C.c_int, [_p, _i32, _i32, _i32, _i32, _i32, _i64, _p, _p, _p]),
+    'clv_qa_head_supported': (C.c_int, [_i32, _i32, _i32]),
+    'clv_qa_head_fwd': (C.c_int, [_p] * 9 + [_f, _f] + [_p] * 5 + [_i32] * 4 + [_p]),
+    'clv_qa_mc_ce_fwd': (C.c_int, [_p] * 4 + [_i32, _i32, _p]),
+    'clv_qa_head_bwd': (C.c_int, [_p] * 14 + [_f] + [_p] * 9 + [_i32] * 4 + [_p]),
+    'clv_attn_probs_mean': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f, _p]),
+    'clv_qa_choice_assemble': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
+    'clv_qa_choice_assemble_bwd': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
 }
 
 _lib = None

@@ -160,6 +160,8 @@ class BertSelfAttention(nn.Module):
             w = torch.cat([self.query.weight, self.key.weight, self.value.weight], dim=0)
             b = torch.cat([self.query.bias, self.key.bias, self.value.bias], dim=0)
         qkv = ops.linear(x, w, b)
+        if getattr(self, '_clv_keep_qkv', False):          # forward_test's attention map (CrossModal..., return_attention)
+            self._clv_qkv = qkv
         return ops.seq_attention(qkv.contiguous(), kmask, self.num_attention_heads,
                                  self.attn_dropout_p if self.training else 0.0)
 

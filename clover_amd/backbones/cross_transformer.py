@@ -4,6 +4,7 @@ with the reference's kwargs and parameter names
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..builder import BACKBONES
 from ..nn import LayerNorm, Linear, to_bf16, trunc_normal_
 from .bert_layers import (BertEmbeddings, BertEncoder, extended_attention_mask, init_bert_weights,
@@ -74,8 +75,19 @@ class CrossModalTransformerFromPretrained(nn.Module):
         mm_mask = torch.cat([torch.ones(B, n_vis, dtype=mask.dtype, device=text.device), mask], dim=1)
         return dict(key=(B, T, S), text=text, pos=pos, mask=mm_mask, ext_mask=extended_attention_mask(mm_mask))
 
-    def forward(self, visual_token=None, text_input_ids=None, text_input_mask=None, text_input_embeds=None, **kwargs):
-        """visual_token [B,T,S,Din]; returns mapping with last/t_/v_last_hidden_state (reference :64-124)."""
+    def forward(self, visual_token=None, text_input_ids=None, text_input_mask=None, text_input_embeds=None,
+                num_choices=1, return_attention=False, **kwargs):
+        """visual_token [B,T,S,Din]; returns mapping with last/t_/v_last_hidden_state (reference :64-124).
+
+        num_choices = C > 1 (multiple-choice QA): visual_token holds ONE entry per video and the text C captions per video
+        ([B*C, L, ...], video-major).  The reference expands the video tokens over the candidates before this module
+        (multimodal_transformer_finetune.py:90-95); fc_in, the position / type embeddings and ``norm`` are per-token, so
+        they run once per video here and only their output is broadcast over the C candidates (the backward sums the C
+        gradients per video before ``norm`` / ``fc_in``).
+        return_attention: also return ``attention`` = the last layer's attention probabilities averaged over the heads,
+        fp32 [B*C, Ltot, Ltot] (``output['attentions'][-1].mean(dim=1)`` of forward_test, :189; inference only)."""
+        if num_choices > 1:
+            return self._forward_choices(visual_token, text_input_mask, text_input_embeds, num_choices, return_attention)
         if self.img_in_size != self.hidden_size:
             visual_token = self.fc_in(visual_token)
         B, T, S, D = visual_token.shape
@@ -111,12 +123,73 @@ class CrossModalTransformerFromPretrained(nn.Module):
             mm_mask = torch.cat([torch.ones(B, n_vis, dtype=text_input_mask.dtype, device=feat.device),
                                  text_input_mask], dim=1)
             ext_mask = extended_attention_mask(mm_mask)
-        h = self.bert_encoder(feat, ext_mask)
+        h = self._encode(feat, ext_mask, return_attention)
         out = {'last_hidden_state': h,
                't_last_hidden_state': h[:, n_vis:],
                'v_last_hidden_state': h[:, :T * S]}
         if self.all_cls_token is not None:
             out['cls_last_hidden_state'] = h[:, n_vis - 1:n_vis]
+        if return_attention:
+            out['attention'] = self._last_attention
+            self._last_attention = None
         if self.return_mask:
             return out, mm_mask
         return out
+
+    def _encode(self, feat, ext_mask, return_attention):
+        if not return_attention:
+            return self.bert_encoder(feat, ext_mask)
+        last = self.bert_encoder.layer[-1].attention.self
+        last._clv_keep_qkv = True
+        try:
+            h = self.bert_encoder(feat, ext_mask)
+            self._last_attention = ops.attn_probs_mean(last._clv_qkv, ext_mask, last.num_attention_heads)
+        finally:
+            last._clv_keep_qkv = False
+            last._clv_qkv = None
+        return h
+
+    def _forward_choices(self, visual_token, text_input_mask, text_embeddings, C, return_attention):
+        if self.use_prompt:
+            raise NotImplementedError('num_choices > 1 with use_prompt=True: no Clover QA config uses prompt tokens')
+        if self.img_in_size != self.hidden_size:
+            visual_token = self.fc_in(visual_token)
+        B, T, S, D = visual_token.shape
+        BC = B * C
+        text_embeddings = text_embeddings.view(BC, -1, text_embeddings.shape[-1])
+        text_input_mask = text_input_mask.view(BC, -1)
+        text_embeddings, pos = self._text_and_pos(text_embeddings, T, S, D)
+        visual = self.norm(to_bf16(visual_token.reshape(B, T * S, D)) + pos)                  # once per video
+        if self.all_cls_token is not None:
+            visual = torch.cat([visual, to_bf16(self.all_cls_token).expand(B, -1, -1)], dim=1)
+        n_vis = visual.shape[1]
+        feat = _ChoiceAssemble.apply(visual, text_embeddings, C)
+        mm_mask = torch.cat([torch.ones(BC, n_vis, dtype=text_input_mask.dtype, device=feat.device), text_input_mask],
+                            dim=1)
+        ext_mask = extended_attention_mask(mm_mask)
+        h = self._encode(feat, ext_mask, return_attention)
+        out = {'last_hidden_state': h, 't_last_hidden_state': h[:, n_vis:], 'v_last_hidden_state': h[:, :T * S]}
+        if self.all_cls_token is not None:
+            out['cls_last_hidden_state'] = h[:, n_vis - 1:n_vis]
+        if return_attention:
+            out['attention'] = self._last_attention
+            self._last_attention = None
+        if self.return_mask:
+            return out, mm_mask
+        return out
+
+
+class _ChoiceAssemble(torch.autograd.Function):
+    """feat [B*C, n_vis + L, D] = [visual[b] ; text[b*C + c]]: the per-video rows broadcast over the C candidates, written
+    by one kernel (clv_qa_choice_assemble); the backward sums the C visual-row gradients of each video and copies the text
+    gradients out in one kernel (clv_qa_choice_assemble_bwd)."""
+
+    @staticmethod
+    def forward(ctx, visual, text, C):
+        ctx.cfg = (visual.shape[0], int(C), visual.shape[1], text.shape[1], visual.shape[2])
+        return ops.choice_assemble(visual, text, C)
+
+    @staticmethod
+    def backward(ctx, d):
+        dv, dt = ops.choice_assemble_bwd(d, ctx.cfg)
+        return dv, dt, None

@@ -59,3 +59,26 @@ class MLMHead(nn.Module):
     def forward(self, sequence_output):
         """[B,L,H] -> prediction scores [B,L,V] (bf16)."""
         return self.predictions(sequence_output)
+
+
+@HEADS.register_module()
+class ITMHead(nn.Module):
+    """Image-text matching head (mmaction/models/heads/mlm_itm_head.py:56-97): Dropout(0.1) -> Linear(D, D) -> Tanh ->
+    Linear(D, 2), parameters ``itm_projector.{1,3}``, xavier / zero init.  The shipped fill-in-the-blank config builds it
+    and never calls it (its parameters get no gradient); the recognizer branches that would call it
+    (multimodal_transformer_finetune.py:108-113, :178-183) are refused, so its forward has no kernel and refuses too."""
+
+    def __init__(self, hidden_dim=768, **kwargs):
+        super().__init__()
+        self.itm_projector = nn.Sequential(nn.Dropout(p=0.1), nn.Linear(hidden_dim, hidden_dim), nn.Tanh(),
+                                           nn.Linear(hidden_dim, 2))
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight)
+                m.bias.data.zero_()
+        self.fp16_enabled = False
+
+    def forward(self, cls_feature):
+        raise NotImplementedError('ITMHead.forward: no shipped Clover config runs the image-text matching head '
+                                  '(answer_cls + itm_head, itm_head without qa_head); it is built for checkpoint '
+                                  'compatibility only')

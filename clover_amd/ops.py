@@ -2581,3 +2581,153 @@ def adamw_step_dev(p, g, m, v, shadow, state, lr, beta1, beta2, eps, weight_deca
     with _Timed('adamw_dev_kernel', 12 * p.numel(), (24 + gbytes + (2 if shadow is not None else 0)) * p.numel()):
         check(fn(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(shadow), _ptr(state), p.numel(),
                  float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), _stream()), 'clv_adamw_step_dev')
+
+
+# --------------------------------------------------------------------------- video QA / fill-in-the-blank (csrc/qa.hip)
+QA_MASK_ID = 103          # BERT [MASK]: the answer row of fill-in-the-blank (multimodal_transformer_finetune.py:100-102)
+
+
+def qa_answer_rows(token_ids, seq_len, base, answer_mask, mask_id=QA_MASK_ID):
+    """The QA head's row table into a fusion output [N, seq_len, D] viewed as [N * seq_len, D], built on the device (no
+    host sync, capturable): row n * seq_len + base (answer_cls), or + the first ``mask_id`` position of caption n
+    (answer_mask).  -> (rows int32 [N], counts int32 [N]: how many ``mask_id`` tokens caption n holds; 1 for answer_cls)."""
+    _need_gpu(token_ids)
+    ids = _c(token_ids.reshape(token_ids.shape[0], -1).long())
+    N, L = ids.shape
+    out = torch.empty(2, N, device=ids.device, dtype=torch.int32)
+    check(_lib.lib().clv_qa_answer_rows(_ptr(ids), N, L, int(seq_len), int(base), int(bool(answer_mask)), int(mask_id),
+                                        _ptr(out[0]), _ptr(out[1]), _stream()), 'clv_qa_answer_rows')
+    return out[0], out[1]
+
+
+def _qa_grad_out(p):
+    """(fp32 buffer the head's backward ADDS the gradient of p into, whether it is the engine's slab sink)."""
+    sink = getattr(p, '_clv_grad', None)
+    if sink is not None:
+        return sink, True
+    return torch.zeros(p.shape, device=p.device, dtype=torch.float32), False
+
+
+class _QAHead(torch.autograd.Function):
+    """QA_MC_head / QA_OE_Head (qa_head.py:8-85) on the rows ``rows`` of h [N, S, D]: dropout -> Linear(D, H) -> LayerNorm
+    -> erf-GELU -> Linear(H, K) as clv_qa_head_fwd (1 launch for K = 1, 2 otherwise), optionally followed by the
+    multiple-choice CrossEntropyLoss over groups of ``C`` rows (clv_qa_mc_ce_fwd, 1 launch).  Backward: one zero fill of
+    d h, clv_qa_head_bwd (2 launches: d h scattered at the rows, the parameter gradients added into the engine's slab sinks
+    or into fresh buffers)."""
+
+    @staticmethod
+    def forward(ctx, h, rows, w1, b1, gamma, beta, w2, b2, seed, drop_p, eps, labels, C):
+        _need_gpu(h, rows)
+        if parity.enabled():
+            raise NotImplementedError('the QA head has no fp32 parity-mode kernels (CLOVER_PARITY): run it on the 16-bit '
+                                      'path')
+        assert h.dtype == BF16, h.dtype
+        h = _c(h)
+        D = h.shape[-1]
+        H, K = w1.shape[0], w2.shape[0]
+        M = rows.numel()
+        if not _lib.lib().clv_qa_head_supported(D, H, K):
+            raise RuntimeError(f'CLV_ERR_UNSUPPORTED: QA head D={D} H={H} K={K} (D <= 1024, H <= 512)')
+        dev = h.device
+        ws = [_c(t.detach().float()) for t in (w1, b1, gamma, beta, w2, b2)]
+        zg = torch.empty(2, M, H, device=dev, dtype=torch.float32)
+        stats = torch.empty(2, M, device=dev, dtype=torch.float32)
+        logits = torch.empty(M, K, device=dev, dtype=torch.float32)
+        L = _lib.lib()
+        check(L.clv_qa_head_fwd(_ptr(h), _ptr(rows), *[_ptr(t) for t in ws], _ptr(seed), float(drop_p), float(eps),
+                                _ptr(zg[0]), _ptr(zg[1]), _ptr(stats[0]), _ptr(stats[1]), _ptr(logits), M, D, H, K,
+                                _stream()), 'clv_qa_head_fwd')
+        ctx.cfg = (h.shape, M, D, H, K, float(drop_p))
+        ctx.params = (w1, b1, gamma, beta, w2, b2)
+        if labels is None:
+            ctx.save_for_backward(h, rows, zg, stats, seed, *ws)
+            ctx.mc = False
+            return logits
+        B = M // C
+        dprob = torch.empty(M, device=dev, dtype=torch.float32)
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        check(L.clv_qa_mc_ce_fwd(_ptr(logits), _ptr(_c(labels.reshape(-1).long())), _ptr(dprob), _ptr(out), B, C,
+                                 _stream()), 'clv_qa_mc_ce_fwd')
+        ctx.save_for_backward(h, rows, zg, stats, seed, *ws, dprob, out)
+        ctx.mc = True
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        shape, M, D, H, K, drop_p = ctx.cfg
+        saved = ctx.saved_tensors
+        h, rows, zg, stats, seed = saved[:5]
+        w1, b1, gamma, beta, w2, b2 = saved[5:11]
+        if ctx.mc:
+            dprob, out = saved[11:]
+            dl, s1, s2 = dprob, out[1:2], _c(dout.float().reshape(1))
+        else:
+            dl, s1, s2 = _c(dout.float()), None, None
+        dev = h.device
+        dh = torch.zeros(shape, device=dev, dtype=h.dtype)
+        scratch = torch.empty(2, M, H, device=dev, dtype=torch.float32)
+        outs = [_qa_grad_out(p) for p in ctx.params]
+        check(_lib.lib().clv_qa_head_bwd(_ptr(h), _ptr(rows), _ptr(w1), _ptr(gamma), _ptr(beta), _ptr(w2), _ptr(zg[0]),
+                                         _ptr(zg[1]), _ptr(stats[0]), _ptr(stats[1]), _ptr(dl), _ptr(s1), _ptr(s2),
+                                         _ptr(seed), drop_p, _ptr(scratch[0]), _ptr(scratch[1]), _ptr(dh),
+                                         *[_ptr(t) for t, _ in outs], M, D, H, K, _stream()), 'clv_qa_head_bwd')
+        grads = []
+        for p, (t, is_sink) in zip(ctx.params, outs):
+            if is_sink:
+                p._clv_ready()
+                grads.append(None)
+            else:
+                grads.append(t.to(p.dtype))
+        return (dh, None, *grads, None, None, None, None, None)
+
+
+def qa_head(h, rows, w1, b1, gamma, beta, w2, b2, drop_p=0.0, eps=1e-5, labels=None, num_choices=None):
+    """h [N, S, D] 16-bit (e.g. the fusion output), rows int32 [M] into h viewed as [N * S, D] -> logits fp32 [M, K]; with
+    ``labels`` (multiple choice, K = 1): the CrossEntropyLoss of the logits viewed [M / num_choices, num_choices]."""
+    seed = next_dropout_seed(h.device) if drop_p > 0 else None
+    if labels is not None:
+        assert w2.shape[0] == 1 and num_choices and rows.numel() % num_choices == 0
+    return _QAHead.apply(h, rows, w1, b1, gamma, beta, w2, b2, seed, float(drop_p), float(eps), labels,
+                         int(num_choices or 1))
+
+
+def choice_assemble(visual, text, C):
+    """visual 16-bit [B, n_vis, D], text [B*C, L, D] -> the multiple-choice fusion input [B*C, n_vis + L, D] (one launch)."""
+    _need_gpu(visual, text)
+    if visual.dtype != BF16 or text.dtype != BF16:
+        raise TypeError(f'choice_assemble takes {BF16} rows, got {visual.dtype} / {text.dtype}')
+    visual, text = _c(visual), _c(text)
+    B, n_vis, D = visual.shape
+    BC, L, _ = text.shape
+    assert BC == B * C and text.shape[2] == D, (visual.shape, text.shape, C)
+    feat = torch.empty(BC, n_vis + L, D, device=visual.device, dtype=visual.dtype)
+    check(_lib.lib().clv_qa_choice_assemble(_ptr(visual), _ptr(text), _ptr(feat), B, int(C), n_vis, L, D, _stream()),
+          'clv_qa_choice_assemble')
+    return feat
+
+
+def choice_assemble_bwd(dfeat, cfg):
+    """-> (d visual [B, n_vis, D]: the sum over the C candidates, d text [B*C, L, D]) (one launch)."""
+    B, C, n_vis, L, D = cfg
+    d = _c(dfeat.to(BF16))
+    dv = torch.empty(B, n_vis, D, device=d.device, dtype=d.dtype)
+    dt = torch.empty(B * C, L, D, device=d.device, dtype=d.dtype)
+    check(_lib.lib().clv_qa_choice_assemble_bwd(_ptr(d), _ptr(dv), _ptr(dt), B, C, n_vis, L, D, _stream()),
+          'clv_qa_choice_assemble_bwd')
+    return dv, dt
+
+
+def attn_probs_mean(qkv, kmask, num_heads):
+    """forward_test's attention map: qkv 16-bit [N, S, 3 C] of a BERT layer, kmask fp32 additive [N, S] (or None) ->
+    fp32 [N, S, S] = softmax(q k^T / sqrt(hd) + kmask) averaged over the heads (inference only: no autograd)."""
+    _need_gpu(qkv)
+    if parity.enabled() or qkv.dtype != BF16:
+        raise NotImplementedError(f'attn_probs_mean reads 16-bit qkv (got {qkv.dtype}); no fp32 parity-mode kernel')
+    qkv = _c(qkv.detach())
+    N, S, C3 = qkv.shape
+    hd = C3 // 3 // num_heads
+    out = torch.empty(N, S, S, device=qkv.device, dtype=torch.float32)
+    km = _c(kmask.detach().float()) if kmask is not None else None
+    check(_lib.lib().clv_attn_probs_mean(_ptr(qkv), _ptr(km), _ptr(out), N, S, num_heads, hd, float(hd) ** -0.5,
+                                         _stream()), 'clv_attn_probs_mean')
+    return out

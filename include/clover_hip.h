@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CLV_ABI_VERSION 17
+#define CLV_ABI_VERSION 18
 #define CLV_ERR_ARG (-1)
 #define CLV_ERR_UNSUPPORTED (-2)
 #define CLV_ERR_LAUNCH (-3)
@@ -598,6 +598,57 @@ int clv_pack_bf16(const float* src, void* dst, int64_t n, void* stream);
 int clv_sumsq_bf16(const void* g, float* acc, int64_t n, void* stream);
 int clv_adamw_step_dev_bf16g(float* p, const void* g, float* m, float* v, void* shadow, const void* state, int64_t n,
                              float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
+/* ------------------------------------------------------------------ video QA / fill-in-the-blank fine-tuning (csrc/qa.hip)
+ * clv_qa_answer_rows: the row table of the QA head into the fusion output [N, Ltot, D] viewed as [N * Ltot, D], built on
+ *   the device from the captions (no host sync, capturable):
+ *     mode 0 (answer_cls, multimodal_transformer_finetune.py:103-107 / :173-177): rows[n] = n * Ltot + base (the text CLS
+ *       row, base = n_vis, or the fusion CLS row, base = n_vis - 1), counts[n] = 1;
+ *     mode 1 (answer_mask, :100-102 / :170-172 `torch.where(token_ids == 103)`): rows[n] = n * Ltot + base + the FIRST
+ *       position l < L with token_ids[n][l] == mask_id, counts[n] = how many there are (the data contract is exactly one;
+ *       a sequence without one points at offset 0).  token_ids int64 [N, L]; counts may be NULL. */
+int clv_qa_answer_rows(const int64_t* token_ids, int32_t N, int32_t L, int32_t Ltot, int32_t base, int32_t mode,
+                       int64_t mask_id, int32_t* rows, int32_t* counts, void* stream);
+/* The fused QA head (QA_MC_head / QA_OE_Head, mmaction/models/heads/qa_head.py:8-85):
+ *   logits = Linear(H, K)(GELU(LayerNorm(Linear(D, H)(Dropout(p)(x[rows])))))  (LayerNorm eps, erf-GELU)
+ * x: bf16 rows of width D (row stride D) addressed by rows int32 [M]; w1 fp32 [H][D], b1 / gamma / beta [H], w2 [K][H],
+ * b2 [K]; seed: the device-resident uint64 dropout seed (keep_scale of (seed, head row, column); NULL when drop_p == 0).
+ * Outputs fp32: z = the Linear(D, H) output and g = GELU(LayerNorm(z)) [M][H], mean / rstd [M], logits [M][K].  Two
+ * launches for K > 1 (row-block kernel + the H -> K GEMM), one for K == 1 (the dot product rides in the row-block kernel).
+ * Supported: D <= 1024, H <= 512 (clv_qa_head_supported). */
+int clv_qa_head_supported(int32_t D, int32_t H, int32_t K);
+int clv_qa_head_fwd(const void* x, const int32_t* rows, const float* w1, const float* b1, const float* gamma,
+                    const float* beta, const float* w2, const float* b2, const uint64_t* seed, float drop_p, float eps,
+                    float* z, float* g, float* mean, float* rstd, float* logits, int32_t M, int32_t D, int32_t H, int32_t K,
+                    void* stream);
+/* Multiple-choice loss (:109-121 `qa_head(x).view(-1, C)` + CrossEntropyLoss): logits fp32 [B][C], labels int64 [B];
+ * out[0] = mean CE over the samples with 0 <= label < C, out[1] = 1 / their count; dprob [B][C] = softmax - onehot (the
+ * loss gradient before out[1] and the incoming gradient).  One launch. */
+int clv_qa_mc_ce_fwd(const float* logits, const int64_t* labels, float* dprob, float* out, int32_t B, int32_t C,
+                     void* stream);
+/* Backward of clv_qa_head_fwd for dlogits = dl [M][K] * (*s1) * (*s2) (either scale pointer may be NULL = 1): the input
+ * gradient is STORED as bf16 into dx_full at rows[i] (the caller zero-fills the rest of it), the parameter gradients are
+ * ADDED into fp32 dw1 [H][D], db1, dgamma, dbeta [H], dw2 [K][H], db2 [K]; dy / dz fp32 [M][H] are scratch.  Two launches;
+ * the dropout mask is regenerated from the forward's seed. */
+int clv_qa_head_bwd(const void* x, const int32_t* rows, const float* w1, const float* gamma, const float* beta,
+                    const float* w2, const float* z, const float* g, const float* mean, const float* rstd, const float* dl,
+                    const float* s1, const float* s2, const uint64_t* seed, float drop_p, float* dy, float* dz,
+                    void* dx_full, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2, float* db2, int32_t M,
+                    int32_t D, int32_t H, int32_t K, void* stream);
+/* Multiple-choice fusion input (multimodal_transformer_finetune.py:90-95 `visual_token.unsqueeze(1).expand(-1, C, ...)` +
+ * cross_transformer.py:112 `torch.cat([visual_token, text_embeddings], dim=1)`): feat bf16 [B*C][n_vis + L][D] =
+ * [visual[b] ; text[b*C + c]] from the per-video rows visual [B][n_vis][D] and the captions text [B*C][L][D].  The
+ * backward writes dvisual [B][n_vis][D] = the sum over the C candidates (fp32, one rounding) and dtext [B*C][L][D].
+ * D % 8 == 0; one launch each. */
+int clv_qa_choice_assemble(const void* visual, const void* text, void* feat, int32_t B, int32_t C, int32_t n_vis,
+                           int32_t L, int32_t D, void* stream);
+int clv_qa_choice_assemble_bwd(const void* dfeat, void* dvisual, void* dtext, int32_t B, int32_t C, int32_t n_vis,
+                               int32_t L, int32_t D, void* stream);
+/* forward_test's `output['attentions'][-1].mean(dim=1)` (:189): from the last fusion layer's packed qkv bf16 [N][S][3 nH hd]
+ * and its additive key mask fp32 [N][S] (may be NULL), out fp32 [N][S][S] = mean over the nH heads of
+ * softmax(q_h k_h^T * scale + kmask).  S <= 4096, hd <= 128 and even. */
+int clv_attn_probs_mean(const void* qkv, const float* kmask, float* out, int32_t N, int32_t S, int32_t nH, int32_t hd,
+                        float scale, void* stream);
 
 #ifdef __cplusplus
 }

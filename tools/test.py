@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""tools/test.py-style evaluation driver for the retrieval task (reference: tools/test.py:27-100 arguments,
+"""tools/test.py-style evaluation driver for the retrieval and video-QA tasks (reference: tools/test.py:27-100 arguments,
 :130-260 main; collection mmaction/core/hooks/my_eval_hook.py:20-100; metrics video_dataset.py:189-195).
 
     python tools/test.py configs/finetune_retrieval_synthetic.py work_dirs/.../epoch_2.pth --eval recall_for_video_text_retrieval
@@ -8,7 +8,12 @@
 The model runs ``forward_test(separate_test=True)`` (the HIP Swin + BERT paths, forward only) over a test set sharded
 rank-major; embeddings are collected over RCCL and rank 0 computes R@1/5/10, median rank.  The dataset side is out of
 scope: ``data.synthetic_test`` describes a synthetic test set (``pairs`` random (clip, caption) pairs, so the metrics
-of an untrained model sit at chance: R@K ~ 100 K / pairs)."""
+of an untrained model sit at chance: R@K ~ 100 K / pairs).
+
+Video QA / fill-in-the-blank (a config with ``evaluation.test_fn='use_itm_head_fn'``, or ``--eval video_qa_mc`` /
+``video_qa_oe``): ``forward_test`` scores every sample (multi_gpu_test_itm_finetune, my_eval_hook.py:317-380) and rank 0
+prints ``acc`` / ``overall_acc`` (video_dataset.py:304-343) over ``data.synthetic_test`` = dict(pairs, frames, tokens,
+qa=dict(num_choices / num_labels / fib)) samples."""
 import argparse
 import json
 import os
@@ -25,7 +30,9 @@ def parse_args():
     p.add_argument('config', help='test config file path')
     p.add_argument('checkpoint', help="checkpoint file ('none' = the seeded random init)")
     p.add_argument('--out', default=None, help='output result file (json)')
-    p.add_argument('--eval', type=str, nargs='+', default=['recall_for_video_text_retrieval'], help='evaluation metrics')
+    p.add_argument('--eval', type=str, nargs='+', default=None,
+                   help='evaluation metrics (default: recall_for_video_text_retrieval; video-QA configs: their '
+                        'evaluation.metrics)')
     p.add_argument('--gpu-collect', action='store_true', help='accepted for CLI compatibility (collection is always RCCL)')
     p.add_argument('--cfg-options', nargs='+', default=[], help='a.b=c overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher')
@@ -35,14 +42,17 @@ def parse_args():
 class SyntheticTestLoader:
     """This rank's shard of a synthetic test set: batches with ``index`` as the reference's test pipeline emits."""
 
-    def __init__(self, pairs, batch, frames, tokens, rank, world, device, seed=4242):
+    def __init__(self, pairs, batch, frames, tokens, rank, world, device, seed=4242, qa=None):
         import bench
+        from clover_amd.utils.qa_synthetic import qa_batch
         self.batches = []
         mine = list(range(rank, pairs, world))
+        keys = ('imgs', 'token_ids', 'segment_ids', 'input_mask') + (('label',) if qa is not None else ())
         for s in range(0, len(mine), batch):
             idx = mine[s:s + batch]
-            b = bench.synthetic_batch(len(idx), frames, tokens, seed + idx[0])
-            b = {k: b[k].to(device) for k in ('imgs', 'token_ids', 'segment_ids', 'input_mask')}
+            b = (qa_batch(len(idx), tokens, frames, seed + idx[0], **qa) if qa is not None
+                 else bench.synthetic_batch(len(idx), frames, tokens, seed + idx[0]))
+            b = {k: b[k].to(device) for k in keys}
             b['index'] = torch.tensor(idx, device=device)
             self.batches.append(b)
 
@@ -53,13 +63,30 @@ class SyntheticTestLoader:
         return iter(self.batches)
 
 
+def select_test(cfg, eval_metrics):
+    """-> ('qa' | 'retrieval', metrics): the video-QA test loop when the config asks for it (evaluation.test_fn ==
+    'use_itm_head_fn', as the reference's tools/test.py) or the metrics are video-QA ones; retrieval otherwise."""
+    from clover_amd.evaluation import QA_METRICS
+    ev = cfg.get('evaluation') or {}
+    qa = ev.get('test_fn') == 'use_itm_head_fn' or any(m in QA_METRICS for m in (eval_metrics or []))
+    if not qa:
+        return 'retrieval', eval_metrics or ['recall_for_video_text_retrieval']
+    metrics = eval_metrics or list(ev.get('metrics', ['video_qa_mc']))
+    bad = [m for m in metrics if m not in QA_METRICS]
+    if bad:
+        raise SystemExit(f'--eval {bad}: a video-QA config evaluates {list(QA_METRICS)}')
+    return 'qa', metrics
+
+
 def main():
     args = parse_args()
     from clover_amd.runner import Config, parse_cfg_options
-    from clover_amd.evaluation import evaluate_retrieval, multi_gpu_test_retrieval
+    from clover_amd.evaluation import (evaluate_qa, evaluate_retrieval, multi_gpu_test_itm_finetune,
+                                       multi_gpu_test_retrieval)
     import clover_amd
     cfg = Config.fromfile(args.config)
     cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
+    kind, metrics = select_test(cfg, args.eval)
     if not torch.cuda.is_available():
         raise SystemExit('tools/test.py needs an MI355X (no CPU fallback)')
     if args.launcher == 'none':
@@ -85,10 +112,13 @@ def main():
     model.eval()
     st = cfg.data.get('synthetic_test', dict(pairs=64, frames=8, tokens=32))
     loader = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
-                                 st.get('tokens', 32), rank, world, dev)
-    results = multi_gpu_test_retrieval(model, loader)
+                                 st.get('tokens', 32), rank, world, dev, qa=st.get('qa') if kind == 'qa' else None)
+    if kind == 'qa':
+        results = multi_gpu_test_itm_finetune(model, loader)
+    else:
+        results = multi_gpu_test_retrieval(model, loader)
     if rank == 0:
-        metrics = evaluate_retrieval(results, args.eval)
+        metrics = (evaluate_qa if kind == 'qa' else evaluate_retrieval)(results, metrics)
         for k, v in metrics.items():
             print(f'{k}: {v:.04f}')                                                   # tools/test.py:255-256
         if args.out:

@@ -33,11 +33,16 @@ def parse_args():
 class SyntheticLoader:
     """`length` batches of synthetic pairs with the layout of the reference's collated batch."""
 
-    def __init__(self, length, batch, frames, tokens, seed, device):
+    def __init__(self, length, batch, frames, tokens, seed, device, qa=None):
         import bench
+        from clover_amd.utils.qa_synthetic import qa_batch
         self.length = length
-        self.batches = [{k: v.to(device) for k, v in bench.synthetic_batch(batch, frames, tokens, seed + i).items()}
-                        for i in range(min(length, 4))]
+
+        def make(i):      # qa: dict(num_choices / num_labels / fib) of a video_qa / FIB config (utils.qa_synthetic)
+            if qa is not None:
+                return qa_batch(batch, tokens, frames, seed + i, **qa)
+            return bench.synthetic_batch(batch, frames, tokens, seed + i)
+        self.batches = [{k: v.to(device) for k, v in make(i).items()} for i in range(min(length, 4))]
 
     def __len__(self):
         return self.length
@@ -83,7 +88,7 @@ def main():
     lr = scaled_lr(cfg, world)                           # tools/train.py:160-166
     syn = cfg.data['synthetic']
     loaders = [SyntheticLoader(s['length'], cfg.get('videos_per_gpu', 1), s.get('frames', 8), s.get('tokens', 32),
-                               1000 * (i + 1) + rank, dev) for i, s in enumerate(syn)]
+                               1000 * (i + 1) + rank, dev, qa=s.get('qa')) for i, s in enumerate(syn)]
     opt, lrc = cfg.optimizer, cfg.lr_config
     engine = CloverEngine(model, next(iter(loaders[0])), lr=lr, betas=tuple(opt.get('betas', (0.9, 0.999))),
                           eps=opt.get('eps', 1e-8), weight_decay=opt.get('weight_decay', 0.0),
