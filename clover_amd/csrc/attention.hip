@@ -26,6 +26,16 @@ constexpr int THREADS = WAVES * 64;
 // kernel; 196-token windows: 50 KB -> three, -7 % / -13 %)
 constexpr int DKV_THREADS(int nkt) { return nkt >= 13 ? 512 : THREADS; }
 
+// ---- host-side tuning numbers (re-tune by editing and A/B-ing two libraries through CLOVER_LIB_PATH)
+// Group slices of the streaming dS sum: 64 groups each (round 5; 16 before).  Every slice's partial sum of every (table row,
+// key) pair is read by the gather, so few long slices (four loads in flight per thread in dbias_sum_kernel) beat many
+// short ones: same-box 11.41 / 11.44 -> 11.29 / 11.34 ms per step.
+constexpr int DBIAS_GROUPS_PER_SLICE = 64;
+// MiB of dS scratch that one chunk of groups may cover (see launch_bwd): same-box A/B: 12.52 -> 12.46 ms per step
+constexpr int DBIAS_CHUNK_MB = 128;
+// heads one wave of the table-gradient gather takes at most (field `pad` of ClvDbiasGather)
+constexpr int DBIAS_HEADS_PER_WAVE = 4;
+
 struct Geom {
     ClvAttnGeom g;
     int nWh, nWw, nW;  // windows per axis / per clip (mode 1)
@@ -1665,12 +1675,8 @@ constexpr int DBIAS_SPLITS = 32;      // group slices of the dS reduction (parti
 
 // bytes of the bf16 dS scratch (16 x 16 fragments of every (group, head)), rounded so that the fp32 dense sums that
 // follow it in `work` stay 256-byte aligned
-// Group slices of the streaming dS sum: 64 groups each (round 5; 16 before).  Every slice's partial sum of every (table row,
-// key) pair is read by the gather, so few long slices (four loads in flight per thread in dbias_sum_kernel) beat many
-// short ones: same-box 11.41 / 11.44 -> 11.29 / 11.34 ms per step.
 inline int dbias_splits(const Geom& G) {
-    static const int gps = getenv("CLV_DBIAS_GROUPS_PER_SLICE") ? atoi(getenv("CLV_DBIAS_GROUPS_PER_SLICE")) : 64;
-    int splits = G.g.groups / (gps > 0 ? gps : 64);
+    int splits = G.g.groups / DBIAS_GROUPS_PER_SLICE;
     return splits < 1 ? 1 : (splits > DBIAS_SPLITS ? DBIAS_SPLITS : splits);
 }
 inline int64_t ds_scratch_bytes(const Geom& G, int nkt) {
@@ -1752,8 +1758,7 @@ int launch_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
 template <int HD, int NKT>
 bool one_eligible(const Geom& G, bool has_bias) {
     if constexpr (HD == 32 && (NKT == 13 || NKT == 25)) {
-        const char* one_env = getenv("CLV_ATTN_BWD_ONE");     // read per call: the tests switch it
-        const int one_mode = one_env ? atoi(one_env) : 1;
+        const int one_mode = clv_env_int("CLV_ATTN_BWD_ONE", 1);     // read per call: the tests switch it
         return one_mode > 0 && G.g.mode == 1 && G.nparts == 1 && !G.drop_thresh &&
                (G.tsplit == 1 || G.g.groups * G.g.nH >= 192 || one_mode > 1) && (G.g.N + 15) / 16 == NKT && has_bias &&
                G.tbn <= 3 * (ONE_CWAVES(NKT) + ONE_SWAVES(NKT)) * 64 && one_lds<HD, NKT>(G.tls) <= MAX_LDS;
@@ -1812,11 +1817,10 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* o, const
     // a 0.5 GB HBM round trip per block that exists only to feed the table gradient.  Run the pair in CHUNKS of groups that
     // reuse one scratch region small enough for the Infinity Cache (256 MB): the sum then reads what the dQ kernel just
     // wrote from the cache, and the next chunk overwrites the same lines before they are ever written back.
-    static const int chunk_mb = getenv("CLV_DBIAS_CHUNK_MB") ? atoi(getenv("CLV_DBIAS_CHUNK_MB")) : 128;      // same-box A/B: 12.52 -> 12.46 ms per step
     int nch = 1;
-    if (bias && (stages & 7) == 7 && chunk_mb > 0 && G.nparts == 1) {
+    if (bias && (stages & 7) == 7 && G.nparts == 1) {
         const int64_t per_group = E * 2;                       // scratch bytes per group
-        while (nch < 8 && (G.g.groups / nch) * per_group > (int64_t)chunk_mb << 20 && G.g.groups % (2 * nch) == 0 &&
+        while (nch < 8 && (G.g.groups / nch) * per_group > (int64_t)DBIAS_CHUNK_MB << 20 && G.g.groups % (2 * nch) == 0 &&
                splits % (2 * nch) == 0)
             nch *= 2;
     }
@@ -2021,34 +2025,30 @@ extern "C" int clv_attn_dbias_gather_batch(const ClvDbiasGather* entries, int32_
         tab.e[i] = en;
     }
     tab.n = n;
-    static const bool presum = !getenv("CLV_DBIAS_PRESUM") || atoi(getenv("CLV_DBIAS_PRESUM")) != 0;
-    static const int hg_max = getenv("CLV_DBIAS_HEADS_PER_WAVE") ? atoi(getenv("CLV_DBIAS_HEADS_PER_WAVE")) : 4;
-    for (int i = 0; i < n; ++i) {                              // heads per wave (field `pad`): only on summed slices
+    for (int i = 0; i < n; ++i) {                              // heads per wave (field `pad`): the gather reads summed slices
         ClvDbiasGather& en = tab.e[i];
         int hg = 1;
-        if (presum || en.nsplit == 1)
-            for (int c = 4; c >= 2; --c)
-                if (c <= hg_max && en.nH % c == 0) { hg = c; break; }
+        for (int c = DBIAS_HEADS_PER_WAVE; c >= 2; --c)
+            if (en.nH % c == 0) { hg = c; break; }
         en.pad = hg;
         en.block_begin = blocks;
         blocks += (en.nslots * (en.nH / hg) + 3) / 4;
     }
-    if (presum) {
-        GatherTable st = tab;
-        int sblocks = 0;
-        bool any = false;
-        for (int i = 0; i < n; ++i) {
-            if ((st.e[i].split_stride & 3) || (reinterpret_cast<uintptr_t>(st.e[i].partial) & 15)) return CLV_ERR_ARG;
-            st.e[i].block_begin = sblocks;
-            sblocks += (int)(((st.e[i].split_stride >> 2) + 255) / 256);
-            any |= st.e[i].nsplit > 1;
-            tab.e[i].nsplit = 1;                                // the gather below reads slice 0 = the sum
-        }
-        if (any) {
-            hipLaunchKernelGGL(dbias_split_sum_batch_kernel, dim3((unsigned)sblocks), dim3(256), 0, (hipStream_t)stream, st);
-            const int rc = clv_check_launch();
-            if (rc) return rc;
-        }
+    // the group slices of every entry are summed into slice 0 first; the gather then reads one slice
+    GatherTable st = tab;
+    int sblocks = 0;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if ((st.e[i].split_stride & 3) || (reinterpret_cast<uintptr_t>(st.e[i].partial) & 15)) return CLV_ERR_ARG;
+        st.e[i].block_begin = sblocks;
+        sblocks += (int)(((st.e[i].split_stride >> 2) + 255) / 256);
+        any |= st.e[i].nsplit > 1;
+        tab.e[i].nsplit = 1;                                    // the gather below reads slice 0 = the sum
+    }
+    if (any) {
+        hipLaunchKernelGGL(dbias_split_sum_batch_kernel, dim3((unsigned)sblocks), dim3(256), 0, (hipStream_t)stream, st);
+        const int rc = clv_check_launch();
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(dbias_gather_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tab);
     return clv_check_launch();

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define CLV_OK 0
 #define CLV_ERR_ARG (-1)
@@ -233,4 +234,11 @@ __device__ __forceinline__ f32x2_t gelu_erf_grad2(f32x2_t x) {
 static inline int clv_check_launch() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? CLV_OK : CLV_ERR_LAUNCH;
+}
+
+// The library reads three environment switches, each one per call because the tests flip it between two live paths:
+// CLV_ATTN_BWD_ONE, CLV_GEMM_SPLITK, CLV_GEMM_ROT ("Environment variables").  Tuning numbers are constexpr.
+static inline int clv_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
 }

@@ -25,6 +25,8 @@ constexpr int FM_C = 96, FM_H = 384, FM_KS = FM_C / 32, FM_CH = FM_H / 32, FM_MT
 constexpr int FM_LD1 = FM_C + 8;        // LDS row of an image with 96 columns (208 B: 16 consecutive rows hit 64 distinct banks)
 constexpr int FM_LD2 = FM_H + 8;        // LDS row of the [96][384] image (784 B: same)
 constexpr int FM_NW = 8;
+constexpr int FM_GRID = 256;           // host: workgroups of a launch at most, one per CU
+// (the ABL template parameters below are compile-time probes that give wrong results: only ABL = 0 is instantiated)
 #ifndef FM_BWD_UNROLL
 #define FM_BWD_UNROLL 2
 #endif
@@ -513,9 +515,8 @@ constexpr size_t FM_LDS_BWD = (size_t)2 * FM_H * FM_LD1 * 2 + FM_H * 4;
 static_assert(FM_LDS_FWD <= 160 * 1024 && FM_LDS_BWD <= 160 * 1024, "both weight images must fit the 160 KB of a CU");
 
 int fm_grid(int64_t M) {
-    static const int per = getenv("CLV_FMLP_GRID") ? atoi(getenv("CLV_FMLP_GRID")) : 256;     // one workgroup per CU
     const int64_t tiles = (M + 15) / 16;
-    return (int)(tiles < per ? tiles : per);
+    return (int)(tiles < FM_GRID ? tiles : FM_GRID);
 }
 
 }  // namespace
@@ -531,14 +532,11 @@ extern "C" int clv_mlp_fused_fwd(const void* a, const void* res, void* sum_out, 
     if (xscale && (!res || rows_per_sample <= 0)) return CLV_ERR_ARG;
     if ((((uintptr_t)a) | ((uintptr_t)res) | ((uintptr_t)sum_out) | ((uintptr_t)w1f) | ((uintptr_t)w2) | ((uintptr_t)out)) & 15)
         return CLV_ERR_ARG;
-    static const int abl = getenv("CLV_FMLP_ABL") ? atoi(getenv("CLV_FMLP_ABL")) : 0;      // probe builds (wrong results)
-    static const int nw = getenv("CLV_FMLP_NW") ? atoi(getenv("CLV_FMLP_NW")) : 8;          // waves per workgroup (= per CU); 12 spills since the row prefetch
-    auto kern = abl == 1 ? &mlp96_fwd_kernel<1, 8> : nw == 8 ? &mlp96_fwd_kernel<0, 8> : &mlp96_fwd_kernel<0, 12>;
-    const int threads = (abl == 1 || nw == 8) ? 512 : 768;
+    auto kern = &mlp96_fwd_kernel<0, 8>;     // eight waves per workgroup (= per CU); twelve spill since the row prefetch
     static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FM_LDS_FWD) == hipSuccess;
-    (void)attr;
-    hipLaunchKernelGGL(kern, dim3((unsigned)fm_grid(M)), dim3(threads), FM_LDS_FWD, (hipStream_t)stream,
+    if (!attr) return CLV_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3((unsigned)fm_grid(M)), dim3(512), FM_LDS_FWD, (hipStream_t)stream,
                        (const bf16_t*)a, (const bf16_t*)res, (bf16_t*)sum_out, mean, rstd, (const bf16_t*)w1f, b1f,
                        (const bf16_t*)w2, b2, (bf16_t*)out, M, eps, xscale, rows_per_sample > 0 ? rows_per_sample : 1);
     return clv_check_launch();
@@ -554,11 +552,10 @@ extern "C" int clv_mlp_fused_bwd(const void* tsum, const float* mean, const floa
     if ((((uintptr_t)tsum) | ((uintptr_t)dout) | ((uintptr_t)dsum) | ((uintptr_t)w1f) | ((uintptr_t)w2t) | ((uintptr_t)da) |
          ((uintptr_t)dres) | ((uintptr_t)act_out) | ((uintptr_t)dpre_out) | ((uintptr_t)xhat_out)) & 15)
         return CLV_ERR_ARG;
-    static const int abl = getenv("CLV_FMLP_ABL") ? atoi(getenv("CLV_FMLP_ABL")) : 0;      // probe builds (wrong results)
-    auto kern = abl == 2 ? &mlp96_bwd_kernel<2> : &mlp96_bwd_kernel<0>;
+    auto kern = &mlp96_bwd_kernel<0>;
     static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FM_LDS_BWD) == hipSuccess;
-    (void)attr;
+    if (!attr) return CLV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((unsigned)fm_grid(M)), dim3(64 * FM_NW), FM_LDS_BWD, (hipStream_t)stream,
                        (const bf16_t*)tsum, mean, rstd, (const bf16_t*)dout, (const bf16_t*)dsum, (const bf16_t*)w1f, b1f,
                        (const bf16_t*)w2t, (bf16_t*)da, (bf16_t*)dres, (bf16_t*)act_out, (bf16_t*)dpre_out,

@@ -909,178 +909,6 @@ int gn_launch_reduce(int epi, hipStream_t st, const float* partial, int S, const
     return clv_check_launch();
 }
 
-// ---------------------------------------------------------------------------------------------------
-// One-tile-per-workgroup version (probe: CLV_GEMM_TILE=lean): ONE 128 x BN tile per 256-thread workgroup (2 x 2 waves), 64-deep stages in a double
-// buffer, two workgroups per CU.  What the SQ counters showed about the first loops applies here as it did to the
-// weight-gradient kernel: per-piece pointer bookkeeping cost several times the 32 MFMAs of a stage.  So: the loop is
-// unrolled over the two slots (every LDS address = per-lane constant + immediate), the 8 DMA pieces of a stage are one
-// asm block in the SGPR-base + 32-bit-VGPR-offset form (a stage advance = two scalar adds per operand), rows past the
-// edge are clamped.  Dispatch order keeps the N tiles of a row block on one XCD (as above).
-template <int BN, int EPI>
-__global__ void __launch_bounds__(256, 2) gemm_nt_lean_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b,
-                                                              const float* __restrict__ bias, const bf16_t* __restrict__ aux,
-                                                              bf16_t* __restrict__ c, bf16_t* __restrict__ c2, int64_t M, int N,
-                                                              int K, int64_t lda, int64_t ldb, int64_t ldc, int tilesN,
-                                                              int nmblk) {
-    constexpr int BM = 128, WAVES = 4;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
-    constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 16, TN = WN / 16;
-    constexpr int PA = BM / (8 * WAVES), PB = BN / (8 * WAVES);            // DMA pieces per wave: 4 and 4 (2)
-    constexpr bool HAS_BIAS = EPI == GN_EPI_BIAS || EPI == GN_EPI_GELU;
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[2 * STAGE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane >> 4, lr = lane & 15;
-    const int xcd = blockIdx.x & 7, xslot = blockIdx.x >> 3;
-    const int mblk = xcd + 8 * (xslot / tilesN), tn = xslot % tilesN;
-    if (mblk >= nmblk) return;
-    const int64_t m0 = (int64_t)mblk * BM;
-    const int n0 = tn * BN;
-    const int wm = (wave >> 1) * WM, wn = (wave & 1) * WN;
-
-    // per-lane source offsets in bytes from the tile's first row (fixed for the whole K loop); the wave's pieces are
-    // consecutive 1-KiB blocks of the operand's LDS image
-    unsigned va[PA], vb[PB];
-#pragma unroll
-    for (int j = 0; j < PA; ++j) {
-        const int r = (wave * PA + j) * 8 + (lane >> 3);                   // LDS row = global row (A)
-        const int cch = (lane & 7) ^ (r & 7);
-        int64_t gr = m0 + r;
-        gr = gr < M ? gr : M - 1;
-        va[j] = (unsigned)(((gr - m0) * lda + cch * 8) * 2);
-    }
-#pragma unroll
-    for (int j = 0; j < PB; ++j) {
-        const int r = (wave * PB + j) * 8 + (lane >> 3);                   // LDS row; global row permuted (see gn_init)
-        const int cch = (lane & 7) ^ (r & 7);
-        const int hh = r / WN, p = r % WN, jj = p >> 4, x = p & 15;
-        int g = n0 + hh * WN + (jj >> 1) * 32 + (x >> 2) * 8 + (jj & 1) * 4 + (x & 3);
-        g = g < N ? g : N - 1;
-        vb[j] = (unsigned)(((int64_t)(g - n0) * ldb + cch * 8) * 2);
-    }
-    const bf16_t* abase = a + m0 * lda;                                    // wave-uniform (SGPR pairs), + 64 per stage
-    const bf16_t* bbase = b + (int64_t)n0 * ldb;
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&ring[0];
-    const unsigned lds_a = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(wave * PA * 1024));
-    const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds0 + A_BYTES + (unsigned)(wave * PB * 1024));
-
-    f32x4_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-    // per-lane fragment addresses inside an operand image: row (w? + t*16 + lr), k chunk ks*4 + lg, XOR (row & 7);
-    // (t*16 + lr) & 7 == lr & 7 and wm, wn are multiples of 8, so one base per k half + immediates t * 2048
-    int fa0[2], fb0[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        fa0[ks] = (wm + lr) * 128 + (((ks * 4 + lg) ^ (lr & 7)) << 4);
-        fb0[ks] = A_BYTES + (wn + lr) * 128 + (((ks * 4 + lg) ^ (lr & 7)) << 4);
-    }
-    auto compute = [&](const unsigned char* st) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            Frag8 fa[TM], fb[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j].u4 = *reinterpret_cast<const uint4*>(st + fb0[ks] + j * 2048);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i].u4 = *reinterpret_cast<const uint4*>(st + fa0[ks] + i * 2048);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = mfma16(fb[j], fa[i], acc[i][j]);   // swapped: D[n][m]
-        }
-    };
-#define GNL_ISSUE(SLOT)                                  \
-    gn_dma_block<PA>(lds_a + (SLOT) * STAGE, va, abase); \
-    gn_dma_block<PB>(lds_b + (SLOT) * STAGE, vb, bbase); \
-    abase += GN_BK;                                      \
-    bbase += GN_BK;
-    const int nst = K / GN_BK;
-    GNL_ISSUE(0)
-    int st = 0;
-    for (; st + 2 <= nst; st += 2) {
-        gn_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();                     // stage st landed everywhere; slot 1 is drained
-        GNL_ISSUE(1)
-        compute(ring);
-        gn_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        if (st + 2 < nst) { GNL_ISSUE(0) }
-        compute(ring + STAGE);
-    }
-    if (st < nst) {                                       // odd stage count: the last one sits in slot 0
-        gn_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        compute(ring);
-    }
-#undef GNL_ISSUE
-
-    // ---- epilogue from registers (see gemm_nt_kernel): accumulator pair (2h, 2h+1) = 8 consecutive columns
-    const int nl = n0 + wn + lg * 8;
-#pragma unroll
-    for (int h = 0; h < TN / 2; ++h) {
-        const int nh = nl + h * 32;
-        if (nh >= N) continue;
-        float bn[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bn[e] = 0.f;
-        if (HAS_BIAS) {                                   // bias as the bf16 operand the library GEMM took
-            const float4 b0 = *reinterpret_cast<const float4*>(bias + nh), b1 = *reinterpret_cast<const float4*>(bias + nh + 4);
-            const float bw[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bn[e] = bf2f(f2bf(bw[e]));
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int64_t m = m0 + wm + i * 16 + lr;
-            if (m >= M) continue;
-            const int64_t g = m * ldc + nh;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = acc[i][2 * h + (e >> 2)][e & 3] + bn[e];
-            if (EPI == GN_EPI_GELU) {
-                *reinterpret_cast<uint4*>(c2 + g) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]),
-                                                               pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2_t r = gelu_erf2((f32x2_t){v[e], v[e + 1]});
-                    v[e] = r.x; v[e + 1] = r.y;
-                }
-            }
-            if (EPI == GN_EPI_DGELU) {
-                const uint4 p = *reinterpret_cast<const uint4*>(aux + g);
-                const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const f32x2_t r = gelu_erf_grad2((f32x2_t){gn_lo(pv[e >> 1]), gn_hi(pv[e >> 1])});
-                    v[e] *= r.x; v[e + 1] *= r.y;
-                }
-            }
-            *reinterpret_cast<uint4*>(c + g) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]),
-                                                          pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-        }
-    }
-}
-
-template <int BN>
-int gn_launch_lean(int epi, hipStream_t st, unsigned grid, const bf16_t* a, const bf16_t* b, const float* bias,
-                   const bf16_t* aux, bf16_t* c, bf16_t* c2, int64_t M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
-                   int tilesN, int nmblk) {
-#define GN_GO(E)                                                                                                       \
-    hipLaunchKernelGGL((gemm_nt_lean_kernel<BN, E>), dim3(grid), dim3(256), 0, st, a, b, bias, aux, c, c2, M, N, K, lda, \
-                       ldb, ldc, tilesN, nmblk)
-    switch (epi) {
-        case GN_EPI_NONE: GN_GO(GN_EPI_NONE); break;
-        case GN_EPI_BIAS: GN_GO(GN_EPI_BIAS); break;
-        case GN_EPI_GELU: GN_GO(GN_EPI_GELU); break;
-        case GN_EPI_DGELU: GN_GO(GN_EPI_DGELU); break;
-        default: return CLV_ERR_UNSUPPORTED;
-    }
-#undef GN_GO
-    return clv_check_launch();
-}
-
 // Batched 2-D transposes of bf16 matrices (the W^T shadows): one 64 x 64 tile per workgroup through LDS, 16-byte
 // accesses on both sides.  Entry e: src [rows][cols] -> dst [cols][rows]; tile_begin = prefix sum of tile counts.
 // The tile is stored with its 8-element column groups XOR-swizzled by the row group (element (r, c) at column c ^ (r & 56)):
@@ -1208,8 +1036,6 @@ int gn_launch_ws(int epi, hipStream_t st, unsigned grid, const bf16_t* a, const 
 // Column partitions of the XCD split (see the kernel): the pc in {1, 2, 4, 8} with the smallest per-XCD operand footprint
 // A_bytes * pc / 8 + B_bytes / pc, among those that leave every XCD at least one column tile.
 int gn_pick_pc(int64_t a_bytes, int64_t b_bytes, int tilesN) {
-    static const int forced = getenv("CLV_GEMM_PC") ? atoi(getenv("CLV_GEMM_PC")) : 0;
-    if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced <= tilesN ? forced : 1;
     int best = 1;
     int64_t best_ws = a_bytes / 8 + b_bytes;
     for (int pc = 2; pc <= 8; pc *= 2) {
@@ -1248,9 +1074,7 @@ extern "C" int clv_gemm_nt_fp8(const void* a8, const void* b8, const float* sa, 
     // the staging code moves bytes: hand it the operands in 2-byte units
 #define GN_ARGS8 epilogue, st, grid, (const bf16_t*)a8, (const bf16_t*)b8, bias, (bf16_t*)c, (bf16_t*)c2, M, N, K / 2, lda / 2, \
                  ldb / 2, ldc, tilesN, nmblk, sa, sb, pc
-    static const int w8 = getenv("CLV_GEMM_W8") ? atoi(getenv("CLV_GEMM_W8")) : 1;     // eight waves, as the bf16 class
-    if (BM == 128 && w8) return gn_launch_fp8<128, 128, 2, 4, 2>(GN_ARGS8);
-    if (BM == 128) return gn_launch_fp8<128, 128, 2, 2, 2>(GN_ARGS8);
+    if (BM == 128) return gn_launch_fp8<128, 128, 2, 4, 2>(GN_ARGS8);     // eight waves, as the bf16 class
     return gn_launch_fp8<64, 128, 2, 2, 3>(GN_ARGS8);
 #undef GN_ARGS8
 }
@@ -1269,11 +1093,6 @@ struct GnPlan {
     int ws;                 // 0: gemm_nt_kernel; 1: gemm_ws_kernel<128,128, 8 consumers + 2 producers>; 2: <64,128, 4 + 2>
 };
 
-int gn_env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 // Measured with cold weights (tools/probes/gemm_lab.cpp, us per launch):
 //  * few rows (M <= 1024: the text tower) — the wave-specialised 64 x 128 class (fc1 10.2 vs 11.2), and for a long
 //    contraction (K >= 1536: 48 tiles x 36-48 stages on 256 CUs) FOUR K slices as work units of their own + the reduce kernel
@@ -1289,13 +1108,11 @@ GnPlan gn_plan(int64_t M, int N, int K, bool allow_split) {
     const int64_t tiles128 = ((M + 127) / 128) * ((N + 127) / 128);
     const int64_t tiles64 = ((M + 63) / 64) * ((N + 127) / 128);
     if (K >= 512 && tiles128 <= 384) p.BM = 64;
-    // probe knobs, read per call (a few getenv: ~0.2 us of host time; the step replays hipGraphs)
-    const int w8 = gn_env_int("CLV_GEMM_W8", 1);
-    const int force_s = gn_env_int("CLV_GEMM_SPLITK", 0);                 // 0: auto, 1: off, n: n slices where allowed
-    const int ws = gn_env_int("CLV_GEMM_WS", 3);                          // bit 0: the 128 x 128 class, bit 1: the few-row class
+    // the two switches the tests flip, read per call (two getenv: ~0.1 us of host time; the step replays hipGraphs)
+    const int force_s = clv_env_int("CLV_GEMM_SPLITK", 0);                // 0: auto, 1: off, n: n slices where allowed
     const int nst = K / GN_BK;
-    p.rot = gn_env_int("CLV_GEMM_ROT", 0) && nst >= 3;                    // measured neutral (hot and cold operands): off
-    if ((ws & 2) && M <= 1024 && K >= 512 && tiles64 <= 256 && N <= GN_MAX_BIAS) {
+    p.rot = clv_env_int("CLV_GEMM_ROT", 0) && nst >= 3;                   // measured neutral (hot and cold operands): off
+    if (M <= 1024 && K >= 512 && tiles64 <= 256 && N <= GN_MAX_BIAS) {
         p.ws = 2;
         p.BM = 64;
         if (allow_split && force_s != 1 && K >= 1536 && tiles64 <= 96) {
@@ -1310,7 +1127,7 @@ GnPlan gn_plan(int64_t M, int N, int K, bool allow_split) {
             while (sk > 2 && nst / sk < 12) --sk;
             p.splitk = sk;
         }
-    } else if ((ws & 1) && tiles128 <= 256 && K >= 1536 && N <= GN_MAX_BIAS) {
+    } else if (tiles128 <= 256 && K >= 1536 && N <= GN_MAX_BIAS) {
         p.ws = 1;
         p.BM = 128;
     }
@@ -1321,7 +1138,7 @@ GnPlan gn_plan(int64_t M, int N, int K, bool allow_split) {
     // 13.4 / 12.8).  N = 1 152 and the M ~ 3 000 shapes lose on it (qkv s2 20.6 -> 23.9, fc2 s3 28.0 -> 39.0).
     // Where the 128 x 192 tiles do not fill the chip once (12 544 rows x 384 columns: 196 tiles), 64 x 192 tiles on four waves,
     // two workgroups per CU: fc2 s2 23.0 -> 21.9, dqkv s2 18.6 -> 17.7, merge s2 14.7 -> 13.5, proj s2 10.2 -> 9.6.
-    if (!p.ws && gn_env_int("CLV_GEMM_T192", 1) && N % 192 == 0 && N <= 576 && M >= 8192) {
+    if (!p.ws && N % 192 == 0 && N <= 576 && M >= 8192) {
         const bool small = ((M + 127) / 128) * (N / 192) <= 256;
         p.BM = small ? 64 : 128;
         p.BN = 192;
@@ -1331,7 +1148,7 @@ GnPlan gn_plan(int64_t M, int N, int K, bool allow_split) {
     }
     if (allow_split && force_s > 1 && nst / force_s >= 2 && K >= 1536 && tiles128 <= 256) p.splitk = force_s;
     if (p.splitk > 1 && !p.ws) p.BM = 128;
-    if (p.BM == 128 && w8 && !p.ws) { p.W = 8; p.r2 = true; }
+    if (p.BM == 128 && !p.ws) { p.W = 8; p.r2 = true; }
     return p;
 }
 
@@ -1347,21 +1164,6 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
     if ((epilogue == GN_EPI_GELU || epilogue == GN_EPI_GELUD) && !c2) return CLV_ERR_ARG;
     if ((epilogue == GN_EPI_DGELU || epilogue == GN_EPI_MUL) && !aux) return CLV_ERR_ARG;
     if (epilogue < GN_EPI_NONE || epilogue > GN_EPI_MUL) return CLV_ERR_UNSUPPORTED;
-    const char* force = getenv("CLV_GEMM_TILE");             // probe override: "128x128", "256x128", "128x128w8"
-    if (force && (!strcmp(force, "lean") || !strcmp(force, "lean64"))) {     // one tile per workgroup (measured 5-15 % behind)
-        // 4 GiB of addressable operand per tile row block (32-bit lane offsets)
-        if ((int64_t)128 * lda * 2 >= (1ll << 31) || (int64_t)128 * ldb * 2 >= (1ll << 31)) return CLV_ERR_UNSUPPORTED;
-        const int BNl = ((force && !strcmp(force, "lean64")) || (N % 128 != 0 && N <= 640)) ? 64 : 128;
-        const int tilesN = (N + BNl - 1) / BNl;
-        const int nmblk = (int)((M + 127) / 128);
-        const unsigned grid = (unsigned)(8 * tilesN * ((nmblk + 7) / 8));
-        hipStream_t st = (hipStream_t)stream;
-        if (BNl == 128)
-            return gn_launch_lean<128>(epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux,
-                                       (bf16_t*)c, (bf16_t*)c2, M, N, K, lda, ldb, ldc, tilesN, nmblk);
-        return gn_launch_lean<64>(epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux,
-                                  (bf16_t*)c, (bf16_t*)c2, M, N, K, lda, ldb, ldc, tilesN, nmblk);
-    }
     // few tiles and a long contraction (Swin stage 3 proj / fc2 / merge, fusion and text encoders: <= 384 tiles of
     // 128 x 128 for 512 workgroup slots): 64 x 128 tiles double the workgroups that share the DMA latency
     // (tools/probes/gemm_tiles.py; with the XCD column split the 450-tile qkv of stage 3 is faster on 128 x 128).
@@ -1371,6 +1173,12 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
     if (pl.splitk > 1 && work_bytes < (int64_t)pl.splitk * M * N * 4) pl = gn_plan(M, N, K, false);
     int BM = pl.BM, BN = pl.BN, W = pl.W;
     bool r2 = pl.r2;
+    hipStream_t st = (hipStream_t)stream;
+#ifdef GN_LAB
+    // Tile lab only (tools/probes/gemm_lab.cpp and the -DGN_LAB variant library of tools/probes/build_wg_variants.sh): a forced
+    // tile class, "<BM>x<BN>[w<waves>][r2]" (the shipped 128 x 128 class is "128x128w8r2") or one of the wave-specialised
+    // names below.  The shipped library compiles none of it.
+    const char* force = getenv("CLV_GEMM_TILE");
     if (force && !strncmp(force, "ws", 2)) {                  // wave-specialised classes (probe names: ws128, ws128c8, ws64, ws64r3)
         const int BMw = strstr(force, "64") ? 64 : 128;
         const int tilesN = (N + 127) / 128;
@@ -1380,7 +1188,6 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
         const int max_units_xcd = ((nmblk + 8 / pc - 1) / (8 / pc)) * ((tilesN + pc - 1) / pc) * pl.splitk;
         const int cap = 32 * (two ? 2 : 1);
         const unsigned grid = (unsigned)(8 * (max_units_xcd < cap ? max_units_xcd : cap));
-        hipStream_t st = (hipStream_t)stream;
 #define GN_WARGS epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, K, \
                  lda, ldb, ldc, tilesN, nmblk, pc, pl.splitk, (float*)work
         if (!strcmp(force, "ws128")) return gn_launch_ws<128, 128, 2, 2, 2, 4>(GN_WARGS);     // 4 consumers (64 x 64) + 2 producers
@@ -1398,37 +1205,38 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
         const char* w = strchr(force, 'w');
         W = w ? atoi(w + 1) : (BM == 256 ? 8 : 4);
         r2 = strstr(force, "r2") != nullptr;
+        pl.ws = 0;                                            // a forced tile runs on gemm_nt_kernel
     }
+#endif
     const int tilesN = (N + BN - 1) / BN;
     const int nmblk = (int)((M + BM - 1) / BM);
-    if (!force && pl.ws) {                                    // wave-specialised classes: one workgroup per CU
+    if (pl.ws) {                                              // wave-specialised classes: one workgroup per CU
         const int pcw = gn_pick_pc((int64_t)M * K * 2, (int64_t)N * K * 2, tilesN);
         const int max_units = ((nmblk + 8 / pcw - 1) / (8 / pcw)) * ((tilesN + pcw - 1) / pcw) * pl.splitk;
         const unsigned gridw = (unsigned)(8 * (max_units < 32 ? max_units : 32));
-        hipStream_t stw = (hipStream_t)stream;
-#define GN_WARGS epilogue, stw, gridw, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, \
+#define GN_WARGS epilogue, st, gridw, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, \
                  K, lda, ldb, ldc, tilesN, nmblk, pcw, pl.splitk, (float*)work
         if (pl.ws == 1) return gn_launch_ws<128, 128, 2, 4, 2, 4>(GN_WARGS);
         return gn_launch_ws<64, 128, 2, 2, 2, 4>(GN_WARGS);
 #undef GN_WARGS
     }
     // persistent workgroups: per_cu per CU, 32 * per_cu slots per XCD, never more than the fullest XCD's units
-    const int per_cu = (BM == 128 && W == 4) ? 2 : (BM == 64 && (BN == 128 || BN == 192)) ? 2 : (BM == 64 && BN == 64) ? 3 : (BM == 128 && W == 8 && r2) ? 2 : 1;
+    const int per_cu = (BM == 64 && (BN == 128 || BN == 192)) ? 2 : (BM == 64 && BN == 64) ? 3 : (BM == 128 && W == 8 && r2) ? 2 : 1;
     const int pc = gn_pick_pc((int64_t)M * K * 2, (int64_t)N * K * 2, tilesN);
     const int max_units_xcd = ((nmblk + 8 / pc - 1) / (8 / pc)) * ((tilesN + pc - 1) / pc) * pl.splitk;
     const unsigned grid = (unsigned)(8 * (max_units_xcd < 32 * per_cu ? max_units_xcd : 32 * per_cu));
-    hipStream_t st = (hipStream_t)stream;
 #define GN_ARGS epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, K, \
                 lda, ldb, ldc, tilesN, nmblk, pc, pl.splitk, pl.rot, (float*)work
-    if (BM == 128 && BN == 128 && W == 4) return gn_launch<128, 128, 2, 2, 2>(GN_ARGS);   // 32 KiB stages x 2, two WGs per CU
-    if (BM == 256 && BN == 128 && W == 8) return gn_launch<256, 128, 4, 2, 3>(GN_ARGS);   // 48 KiB stages x 3
     if (BM == 128 && BN == 128 && W == 8 && r2) return gn_launch<128, 128, 2, 4, 2>(GN_ARGS);   // 32 KiB stages x 2, two WGs per CU
-    if (BM == 128 && BN == 128 && W == 8) return gn_launch<128, 128, 2, 4, 4>(GN_ARGS);   // 32 KiB stages x 4
     if (BM == 64 && BN == 128 && W == 4) return gn_launch<64, 128, 2, 2, 3>(GN_ARGS);     // 24 KiB stages x 3, two WGs per CU
-    if (BM == 64 && BN == 128 && W == 8) return gn_launch<64, 128, 2, 4, 3>(GN_ARGS);     // the same ring on eight waves of 32 x 32
-    if (BM == 64 && BN == 64 && W == 2) return gn_launch<64, 64, 1, 2, 3>(GN_ARGS);       // 16 KiB stages x 3, three WGs per CU
     if (BM == 128 && BN == 192 && W == 8) return gn_launch<128, 192, 4, 2, 3>(GN_ARGS);   // 40 KiB stages x 3, eight waves of 32 x 96
     if (BM == 64 && BN == 192 && W == 4) return gn_launch<64, 192, 2, 2, 2>(GN_ARGS);     // 32 KiB stages x 2, four waves of 32 x 96, two WGs per CU
+#ifdef GN_LAB
+    if (BM == 256 && BN == 128 && W == 8) return gn_launch<256, 128, 4, 2, 3>(GN_ARGS);   // 48 KiB stages x 3
+    if (BM == 128 && BN == 128 && W == 8) return gn_launch<128, 128, 2, 4, 4>(GN_ARGS);   // 32 KiB stages x 4
+    if (BM == 64 && BN == 128 && W == 8) return gn_launch<64, 128, 2, 4, 3>(GN_ARGS);     // the same ring on eight waves of 32 x 32
+    if (BM == 64 && BN == 64 && W == 2) return gn_launch<64, 64, 1, 2, 3>(GN_ARGS);       // 16 KiB stages x 3, three WGs per CU
+#endif
 #undef GN_ARGS
     return CLV_ERR_UNSUPPORTED;
 }

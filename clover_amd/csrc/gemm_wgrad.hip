@@ -15,6 +15,12 @@
 namespace {
 
 constexpr int WG_THREADS = 256;
+// ---- host-side tuning numbers of the grouped launch (re-tune by editing and A/B-ing two libraries through CLOVER_LIB_PATH)
+// workgroups a grouped launch aims at in total, shared among its problems (~8 per CU), and the floor per problem
+constexpr int WG_GROUP_TARGET = 2048, WG_TARGET_MIN = 64;
+// the same for the 256 x 256 class; few wide-tile problems: long slices beat more partials (-0.05 ms), hence the cap
+constexpr int WG_BIG_GROUP_TARGET = 1024, WG_BIG_TARGET_MIN = 24, WG_BIG_TARGET_MAX = 48;
+constexpr int WG_MIN_SLICE_ROWS = 256;                     // rows an M-slice keeps at least
 constexpr int TN = 128, TK = 128, TM = 64;
 constexpr int LD = 128 + 16;   // row stride 72 dwords = 8 banks: the 4 rows x 32 B of a transpose read tile the banks
 constexpr int CHUNKS = TM * (128 / 8) / WG_THREADS;       // 16-B chunks per thread per tile (= 4)
@@ -177,142 +183,8 @@ template <int N_>
 __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
 }
-__device__ __forceinline__ uint2 tr4s(const bf16_t* base, int row, int c0, int lr) {
-    // rows row..row+3 (lane lr>>2), columns c0 + (lr&3)*4 .. +4 of the swizzled [SM][128] stage
-    const int r = row + (lr >> 2);
-    const bf16_t* p = base + r * 128 + ((((c0 >> 4) ^ (r & 7)) << 4) | ((lr & 3) << 2));
-    const v4s_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)p);
-    union { v4s_t v; uint2 u; } cv;
-    cv.v = v;
-    return cv.u;
-}
-
-template <bool ACCUM>
-__global__ void __launch_bounds__(WG_THREADS, 2) wgrad_dma_kernel(const bf16_t* __restrict__ dy,
-                                                                  const bf16_t* __restrict__ x,
-                                                                  float* __restrict__ out, float* __restrict__ out_b,
-                                                                  int64_t M, int N, int K, int ldy, int ldx, int tiles,
-                                                                  int tilesK, int nsplits, int64_t rows_per_split,
-                                                                  int want_bias) {
-    __shared__ __attribute__((aligned(1024))) bf16_t ring[RING][2][STAGE];   // [slot][dY | X]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane >> 4, lr = lane & 15;
-    // Workgroup i runs on XCD i % 8 (round-robin dispatch).  All output tiles of one M-slice are placed on ONE
-    // XCD, in consecutive slots, so the dY / X rows they share come from HBM once and are re-read from that
-    // XCD's L2 (the slices' workgroups start together and walk their rows at the same pace).
-    // (nsplits < 0: plain order — few slices, or few tiles per slice, where spreading over all XCDs wins.)
-    int split, tile;
-    if (nsplits > 0) {
-        const int xcd = blockIdx.x & 7, xslot = blockIdx.x >> 3;
-        split = xcd + 8 * (xslot / tiles);
-        tile = xslot % tiles;
-        if (split >= nsplits) return;
-    } else {
-        split = blockIdx.x / tiles;
-        tile = blockIdx.x - split * tiles;
-    }
-    const int tn = tile / tilesK, tk = tile - tn * tilesK;
-    const int n0 = tn * TN, k0 = tk * TK;
-    const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-    const int64_t m_begin = (int64_t)split * rows_per_split;
-    int64_t m_end = m_begin + rows_per_split;
-    if (m_end > M) m_end = M;
-    const bool do_bias = want_bias && tk == 0 && wk == 0;
-
-    // this lane's two chunks per tensor per stage: LDS position p = j*256 + tid -> row p>>4, physical chunk p&15
-    const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero16);
-    int rowj[2];
-    const bf16_t *sy[2], *sx[2];
-    bool vy[2], vx[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int p = j * 256 + tid;
-        const int r = p >> 4, c = ((p & 15) ^ ((r & 7) << 1)) * 8;
-        rowj[j] = r;
-        vy[j] = n0 + c < N;
-        vx[j] = k0 + c < K;
-        sy[j] = dy + (m_begin + r) * ldy + n0 + c;
-        sx[j] = x + (m_begin + r) * ldx + k0 + c;
-    }
-    const unsigned ring_base = __builtin_amdgcn_readfirstlane(
-        (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16_t*)&ring[0][0][0] + (unsigned)wave * 1024u);
-    // every stage is issued as exactly 4 pieces per wave, also past m_end (all-zero source), so that the
-    // counted waits below stay uniform
-    auto issue = [&](int slot, int64_t m0) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const bool in = m0 + rowj[j] < m_end;
-            dma16((in && vy[j]) ? sy[j] : zero, ring_base + (unsigned)((slot * 2 + 0) * STAGE * 2 + j * 4096));
-            dma16((in && vx[j]) ? sx[j] : zero, ring_base + (unsigned)((slot * 2 + 1) * STAGE * 2 + j * 4096));
-            sy[j] += (int64_t)SM * ldy;
-            sx[j] += (int64_t)SM * ldx;
-        }
-    };
-
-    f32x4_t acc[4][4];
-    f32x4_t bacc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        bacc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    }
-    Frag8 ones;
-    ones.u[0] = ones.u[1] = ones.u[2] = ones.u[3] = CLV_ONE_PAIR;
-
-#pragma unroll
-    for (int d = 0; d < RING - 1; ++d) issue(d, m_begin + d * SM);
-    int slot = 0;
-    for (int64_t m0 = m_begin; m0 < m_end; m0 += SM) {
-        wait_vm<(RING - 2) * 4>();       // this wave's pieces of stage m0 have landed (RING-2 later stages may fly on)
-        __builtin_amdgcn_s_barrier();    // ... and every other wave's; everyone is also done reading the previous slot
-        issue(slot == 0 ? RING - 1 : slot - 1, m0 + (int64_t)(RING - 1) * SM);
-        const bf16_t* Ys = ring[slot][0];
-        const bf16_t* Xs = ring[slot][1];
-        slot = slot == RING - 1 ? 0 : slot + 1;
-        Frag8 a[4], b[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a[i].u2[0] = tr4s(Ys, lg * 4, wn + i * 16, lr);
-            a[i].u2[1] = tr4s(Ys, 16 + lg * 4, wn + i * 16, lr);
-            b[i].u2[0] = tr4s(Xs, lg * 4, wk + i * 16, lr);
-            b[i].u2[1] = tr4s(Xs, 16 + lg * 4, wk + i * 16, lr);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
-            if (do_bias) bacc[i] = mfma16(a[i], ones, bacc[i]);
-        }
-    }
-    wait_vm<0>();                        // drain the all-zero tail stages before the LDS is released
-    // ACCUM: out = dW (+=), out_b = db (+=).  Otherwise out = this split's partial [N*K dW | N db].
-    float* pw = ACCUM ? out : out + (int64_t)split * ((int64_t)N * K + N);
-    float* pb = ACCUM ? out_b : pw + (int64_t)N * K;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = n0 + wn + i * 16 + lg * 4 + r;
-            if (n >= N) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = k0 + wk + j * 16 + lr;
-                if (k < K) {
-                    // ACCUM: this workgroup is the only writer of the element; the no-return L2 atomic is
-                    // fire-and-forget, where "+=" would be 64 dependent load -> add -> store round trips
-                    if (ACCUM) atomicAdd(&pw[(int64_t)n * K + k], acc[i][j][r]);
-                    else pw[(int64_t)n * K + k] = acc[i][j][r];
-                }
-            }
-            if (do_bias && lr == 0) {
-                if (ACCUM) atomicAdd(&pb[n], bacc[i][r]);
-                else pb[n] = bacc[i][r];
-            }
-        }
-}
-
 // ---------------------------------------------------------------------------------------------------
-// Lean-loop version of wgrad_dma_kernel (same tiling, ring, swizzle and output).  The first version spent ~70 VALU and
+// The LDS-DMA weight-gradient loop (second generation; the first was removed, see history).  The first version spent ~70 VALU and
 // ~50 SALU instructions per 32-row stage on per-piece pointer selects / 64-bit increments / bounds predicates / slot
 // arithmetic around its 16-20 MFMAs (rocprofv3 SQ counters: 3 445 VALU + 2 490 SALU per 49-stage wave) and, with one
 // wave per SIMD, ran at ~1 700 cycles per stage.  Here:
@@ -358,9 +230,14 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
                                                 int ldy, int ldx, int tiles, int tilesK, int nsplits,
                                                 int64_t rows_per_split, int want_bias, int xcd_rot = 0,
                                                 int overwrite = 0, float* __restrict__ ssq = nullptr) {
+    static_assert(ACCUM == RMW, "in place = one M-slice read-modify-written; otherwise partials for the fold");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lg = lane >> 4, lr = lane & 15;
     int split, tile;
-    if (nsplits > 0 && xcd_rot >= 0) {                                       // see wgrad_dma_kernel
+    // Workgroup i runs on XCD i % 8 (round-robin dispatch).  All output tiles of one M-slice are placed on ONE
+    // XCD, in consecutive slots, so the dY / X rows they share come from HBM once and are re-read from that
+    // XCD's L2 (the slices' workgroups start together and walk their rows at the same pace).
+    // (nsplits < 0 or xcd_rot < 0: plain order — few slices, or few tiles per slice, where spreading over all XCDs wins.)
+    if (nsplits > 0 && xcd_rot >= 0) {
         const int xcd = (bid - xcd_rot) & 7, xslot = bid >> 3;               // grouped launches rotate the XCDs per problem
         split = xcd + 8 * (xslot / tiles);
         tile = xslot % tiles;
@@ -380,73 +257,6 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
     const int rows = (int)(m_end - m_begin);
     const int nst = (rows + SM - 1) / SM;                   // stages of this slice
     const int nfull = rows / SM;                            // ... of which complete (all 32 rows inside)
-    // Wave-specialised launch (blockDim = 320): a FIFTH wave issues every LDS-DMA piece of the workgroup, the four MFMA
-    // waves only read and multiply.  A wave is blocked ~60 cycles per piece it issues (the CU's vector-memory path takes
-    // 1 KiB per ~16 cycles) and feeds no MFMA meanwhile — tools/probes/gemm_lab.cpp measured issue ~ compute ~ 40 % of a
-    // stage each for this loop structure; on separate waves the two overlap.
-    const bool ws = blockDim.x > WG_THREADS;
-    if (ws && wave == 4) {
-        const int ln = lane;
-        unsigned py[8], px[8];
-        int prow[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {                       // q = j * 4 + w: the piece wave w issued as its j-th
-            const int pp = (q >> 2) * 256 + (q & 3) * 64 + ln;
-            const int r = pp >> 4, c = ((pp & 15) ^ ((r & 7) << 1)) * 8;
-            int cy = n0 + c, cx = k0 + c;
-            cy = cy < N ? cy : N - 8;
-            cx = cx < K ? cx : K - 8;
-            prow[q] = r;
-            py[q] = (unsigned)((r * ldy + cy) * 2);
-            px[q] = (unsigned)((r * ldx + cx) * 2);
-        }
-        const bf16_t* pby = dy + m_begin * ldy;
-        const bf16_t* pbx = x + m_begin * ldx;
-        const int64_t sy = (int64_t)SM * ldy, sx = (int64_t)SM * ldx;
-        const unsigned lds0 = __builtin_amdgcn_readfirstlane(
-            (unsigned)(uintptr_t)(__attribute__((address_space(3))) bf16_t*)&ring[0][0][0]);
-        const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero16);
-        auto issue_p = [&](int s, int slot) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const bool in = s * SM + prow[q] < rows;
-                const unsigned dst = lds0 + (unsigned)((q & 3) * 1024 + (q >> 2) * 4096);
-                dma16(in ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pby) + py[q]) : zero,
-                      dst + (unsigned)((slot * 2 + 0) * STAGE * 2));
-                dma16(in ? reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(pbx) + px[q]) : zero,
-                      dst + (unsigned)((slot * 2 + 1) * STAGE * 2));
-            }
-            pby += sy;
-            pbx += sx;
-        };
-        // complete stages go out in the lean form (SGPR bases + fixed lane offsets, four pieces per asm block), the ragged
-        // last one through the predicated per-piece path
-        auto issue_f = [&](int s, int slot) {
-            if (s < nfull) {
-                const int sc = slot * 2 * STAGE * 2;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) dma4(lds0 + (unsigned)(w * 1024), py[w], py[4 + w], px[w], px[4 + w], pby, pbx, sc);
-                pby += sy;
-                pbx += sx;
-            } else {
-                issue_p(s, slot);
-            }
-        };
-        for (int d = 0; d < RING - 1 && d < nst; ++d) issue_f(d, d);
-        int nslot = (RING - 1) % RING;
-        for (int s = 0; s < nst; ++s) {
-            if (nst - 1 - s >= RING - 2) wait_vm<(RING - 2) * 16>();
-            else wait_vm<0>();
-            __builtin_amdgcn_s_barrier();
-            if (s + RING - 1 < nst) {
-                issue_f(s + RING - 1, nslot);
-                nslot = nslot == RING - 1 ? 0 : nslot + 1;
-            }
-        }
-        wait_vm<0>();
-        return;
-    }
-
     // per-lane source offsets (bytes from the stage's first row), fixed for the whole slice: LDS position
     // p = j*256 + tid -> row p>>4, physical chunk p&15 holds logical chunk (p&15) ^ ((row&7)<<1); columns clamped
     unsigned vy[2], vx[2];
@@ -525,29 +335,11 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[i][j] = (ACCUM && !RMW) ? mfma16(a[i], b[j], acc[i][j])   // D[n][k]: atomics coalesce along k across lanes
-                                            : mfma16(b[j], a[i], acc[i][j]);  // swapped, D[k][n]: 4 consecutive k per lane
-            if (do_bias) bacc[i] = (ACCUM && !RMW) ? mfma16(a[i], ones, bacc[i]) : mfma16(ones, a[i], bacc[i]);
+                acc[i][j] = mfma16(b[j], a[i], acc[i][j]);  // swapped, D[k][n]: 4 consecutive k per lane
+            if (do_bias) bacc[i] = mfma16(ones, a[i], bacc[i]);
         }
     };
 
-    if (ws) {                                               // MFMA waves of a wave-specialised workgroup
-        int sw = 0;
-        for (; sw + RING <= nst; sw += RING) {
-            __builtin_amdgcn_s_barrier(); compute(ring[0][0], ring[0][1]);
-            __builtin_amdgcn_s_barrier(); compute(ring[1][0], ring[1][1]);
-            __builtin_amdgcn_s_barrier(); compute(ring[2][0], ring[2][1]);
-#if WG_RING == 4
-            __builtin_amdgcn_s_barrier(); compute(ring[3][0], ring[3][1]);
-#endif
-        }
-        int sl = 0;
-        for (; sw < nst; ++sw) {
-            __builtin_amdgcn_s_barrier();
-            compute(ring[sl][0], ring[sl][1]);
-            sl = sl == RING - 1 ? 0 : sl + 1;
-        }
-    } else {
 #pragma unroll
     for (int d = 0; d < RING - 1; ++d) issue_slow(d);       // prologue (also correct for slices shorter than the ring)
     int st = 0;
@@ -589,10 +381,9 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
         slot = slot == RING - 1 ? 0 : slot + 1;
     }
     wait_vm<0>();
-    }
     float* pw = ACCUM ? out : out + (int64_t)split * ((int64_t)N * K + N);
     float* pb = ACCUM ? out_b : pw + (int64_t)N * K;
-    if (ACCUM && RMW) {
+    if (ACCUM) {
         // one M-slice: this workgroup is the only writer of its dW elements in this launch (and the engine orders the
         // launches that share a parameter), so "+=" is a 16-byte load / add / store per lane in the swapped layout —
         // 2 x 4 B of traffic per element instead of a memory-side atomic each (~190 G/s: 12 us for a 768 x 3072 matrix).
@@ -622,22 +413,6 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
             if (do_bias && lg == 0) pb[n] += bacc[i][0];
         }
         if (ssq && (overwrite & 4)) ssq_commit(ssq, ssq_q);       // (wave-uniform condition)
-    } else if (ACCUM) {
-        // acc[i][j][r] = dW[n0 + wn + i*16 + lg*4 + r][k0 + wk + j*16 + lr]: this workgroup is the only writer of the
-        // element; the no-return L2 atomic is a fire-and-forget "+=", one instruction = 4 rows x 64 contiguous bytes
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + wn + i * 16 + lg * 4 + r;
-                if (n >= N) continue;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = k0 + wk + j * 16 + lr;
-                    if (k < K) atomicAdd(&pw[(int64_t)n * K + k], acc[i][j][r]);
-                }
-                if (do_bias && lr == 0) atomicAdd(&pb[n], bacc[i][r]);
-            }
     } else {
         // swapped MFMA: acc[i][j][r] = dW[n0 + wn + i*16 + lr][k0 + wk + j*16 + lg*4 + r] — a lane owns 4 consecutive k:
         // one 16-byte store per (i, j), the 4 lanes of a row write 64 contiguous bytes (K % 8 == 0)
@@ -658,7 +433,7 @@ __device__ __forceinline__ void wgrad_dma2_body(bf16_t (&ring)[RING][2][STAGE], 
 }
 
 template <bool ACCUM, bool RMW = false>
-__global__ void __launch_bounds__(WG_THREADS + 64, 2) wgrad_dma2_kernel(const bf16_t* __restrict__ dy,
+__global__ void __launch_bounds__(WG_THREADS, 2) wgrad_dma2_kernel(const bf16_t* __restrict__ dy,
                                                                    const bf16_t* __restrict__ x,
                                                                    float* __restrict__ out, float* __restrict__ out_b,
                                                                    int64_t M, int N, int K, int ldy, int ldx, int tiles,
@@ -689,7 +464,7 @@ struct WgGroup {
     int n;
     float* ssq;                                              // norm slots (ssq_commit) or nullptr
 };
-__global__ void __launch_bounds__(WG_THREADS + 64, 2) wgrad_dma2_group_kernel(WgGroup grp) {
+__global__ void __launch_bounds__(WG_THREADS, 2) wgrad_dma2_group_kernel(WgGroup grp) {
     __shared__ __attribute__((aligned(1024))) bf16_t ring[RING][2][STAGE];
     int idx = 0;
     for (int i = 1; i < grp.n; ++i)
@@ -1073,9 +848,8 @@ int pick_splits(int64_t M, int tiles) {
     if (M <= 1024) return 1;                            // few rows: one slice, accumulate directly (no partials)
     // ~1 workgroup per CU: every extra slice costs N*K*4 bytes of partial traffic (store + fold), which for the
     // square-ish layers (stage 3, fusion: 144 tiles) is what the kernel's time consists of
-    if (const char* f = getenv("CLV_WGRAD_SPLITS")) return atoi(f) < (M + 255) / 256 ? atoi(f) : (int)((M + 255) / 256);
     int64_t s = (256 + tiles - 1) / tiles;
-    if (tiles >= 4 && tiles <= 40) s = (s + 7) / 8 * 8; // whole M-slices per XCD (see wgrad_dma_kernel), while that rounding is cheap
+    if (tiles >= 4 && tiles <= 40) s = (s + 7) / 8 * 8; // whole M-slices per XCD (see wgrad_dma2_body), while that rounding is cheap
     const int64_t max_by_rows = (M + 255) / 256;        // >= 256 rows per slice
     if (s > max_by_rows) s = max_by_rows;
     if (s < 1) s = 1;
@@ -1083,13 +857,6 @@ int pick_splits(int64_t M, int tiles) {
 }
 
 }  // namespace
-
-// CLV_WGRAD_WS=1 (probe): 320 threads = four MFMA waves + one LDS-DMA producer wave (wgrad_dma2_body).  Measured and NOT
-// the default: with two workgroups per CU the other workgroup already fills the issue bubbles — 11.89 vs 11.83 ms per step.
-static unsigned wg_threads() {
-    const char* v = getenv("CLV_WGRAD_WS");
-    return (v && atoi(v) == 1) ? WG_THREADS + 64 : WG_THREADS;
-}
 
 extern "C" int64_t clv_linear_wgrad_work_floats(int64_t M, int32_t N, int32_t K) {
     const int tiles = ((N + TN - 1) / TN) * ((K + TK - 1) / TK);
@@ -1110,12 +877,10 @@ extern "C" int clv_linear_wgrad(const void* dy, const void* x, float* dw, float*
     const int splits = pick_splits(M, tiles);
     int64_t rows = (M + splits - 1) / splits;
     rows = (rows + TM - 1) / TM * TM;
-    // up to 24 slices add their tiles into dW with no-return fp32 atomics (measured: cheaper than partials + fold;
-    // with more slices the same-address contention at the memory-side atomic units costs more than the fold)
-    // one slice: its tiles are added straight into dW (no-return fp32 atomics as fire-and-forget read-modify-writes);
-    // several slices: fp32 partials + a streaming fold — atomics into dW from every slice measured 2x slower than the
-    // whole rest of the kernel (190 G atomics/s: 25 us for the 18.9 MB of a stage-2 fc1, 50 us for a stage-3 fc1)
-    const bool atomic_acc = getenv("CLV_WGRAD_ATOMIC") ? splits <= 24 : splits == 1;
+    // one slice: its tiles are read-modify-written straight into dW; several slices: fp32 partials + a streaming fold —
+    // atomics into dW from every slice measured 2x slower than the whole rest of the kernel (190 G atomics/s: 25 us for
+    // the 18.9 MB of a stage-2 fc1, 50 us for a stage-3 fc1)
+    const bool in_place = splits == 1;
     const bf16_t* dyp = (const bf16_t*)dy;
     const bf16_t* xp = (const bf16_t*)x;
     int rc = CLV_OK;
@@ -1127,27 +892,17 @@ extern "C" int clv_linear_wgrad(const void* dy, const void* x, float* dw, float*
         if (xmean) {                       // standardise-on-load needs the register-staged kernel
             hipLaunchKernelGGL(wgrad_kernel, dim3(total), dim3(WG_THREADS), 0, st, dyp, xp, work, M, (int)N, (int)K,
                                (int)ldy, (int)ldx, tiles, tilesK, rows, db ? 1 : 0, xmean, xrstd);
-        } else if (getenv("CLV_WGRAD_OLD")) {                                       // A/B switch: the first version
-            if (atomic_acc)
-                hipLaunchKernelGGL(wgrad_dma_kernel<true>, dim3(dma_grid), dim3(WG_THREADS), 0, st, dyp, xp, dw, db, M,
-                                   (int)N, (int)K, (int)ldy, (int)ldx, tiles, tilesK, nsp, rows, db ? 1 : 0);
-            else
-                hipLaunchKernelGGL(wgrad_dma_kernel<false>, dim3(dma_grid), dim3(WG_THREADS), 0, st, dyp, xp, work, nullptr,
-                                   M, (int)N, (int)K, (int)ldy, (int)ldx, tiles, tilesK, nsp, rows, db ? 1 : 0);
-        } else if (atomic_acc && splits == 1 && !getenv("CLV_WGRAD_NORMW")) {   // one M-slice: dW += in place, no fold
-            hipLaunchKernelGGL((wgrad_dma2_kernel<true, true>), dim3(dma_grid), dim3(wg_threads()), 0, st, dyp, xp, dw, db, M,
-                               (int)N, (int)K, (int)ldy, (int)ldx, tiles, tilesK, nsp, rows, db ? 1 : 0);
-        } else if (atomic_acc) {           // A/B switches: atomics straight into dW / db
-            hipLaunchKernelGGL(wgrad_dma2_kernel<true>, dim3(dma_grid), dim3(wg_threads()), 0, st, dyp, xp, dw, db, M,
+        } else if (in_place) {             // one M-slice: dW += in place, no fold
+            hipLaunchKernelGGL((wgrad_dma2_kernel<true, true>), dim3(dma_grid), dim3(WG_THREADS), 0, st, dyp, xp, dw, db, M,
                                (int)N, (int)K, (int)ldy, (int)ldx, tiles, tilesK, nsp, rows, db ? 1 : 0);
         } else {
-            hipLaunchKernelGGL(wgrad_dma2_kernel<false>, dim3(dma_grid), dim3(wg_threads()), 0, st, dyp, xp, work, nullptr,
+            hipLaunchKernelGGL(wgrad_dma2_kernel<false>, dim3(dma_grid), dim3(WG_THREADS), 0, st, dyp, xp, work, nullptr,
                                M, (int)N, (int)K, (int)ldy, (int)ldx, tiles, tilesK, nsp, rows, db ? 1 : 0);
         }
         rc = clv_check_launch();
         if (rc) return rc;
     }
-    if ((stages & 2) && !(atomic_acc && !xmean)) {
+    if ((stages & 2) && !(in_place && !xmean)) {
         const int64_t NK = (int64_t)N * K, E2 = NK + N;
         const int64_t Eeff = db ? E2 : NK;
         const int64_t groups = (Eeff + 3) / 4;               // threads needed with one slice-lane
@@ -1207,19 +962,13 @@ extern "C" int clv_wgrad_fold_batch_ss(const ClvFoldEntry* entries, int32_t n, f
 }
 
 // Slices of one problem inside a grouped launch of n problems: enough workgroups in total (~8 per CU) rather than per
-// problem, at least 256 rows per slice.
+// problem, at least WG_MIN_SLICE_ROWS rows per slice.
 static int group_splits(int64_t M, int tiles, int n, int cls = 0) {
-    int64_t target = (cls ? 1024 : 2048) / (n > 0 ? n : 1);
-    if (target < (cls ? 24 : 64)) target = cls ? 24 : 64;
-    if (cls && target > 48) target = 48;                     // few wide-tile problems: long slices beat more partials (-0.05 ms)
-    static const int env_big = getenv("CLV_WGRAD_BIG_TARGET") ? atoi(getenv("CLV_WGRAD_BIG_TARGET")) : 0;
-    if (cls && env_big > 0) target = env_big;
-    static const int env_target = getenv("CLV_WGRAD_GROUP_TARGET") ? atoi(getenv("CLV_WGRAD_GROUP_TARGET")) : 0;
-    static const int env_rows = getenv("CLV_WGRAD_GROUP_ROWS") ? atoi(getenv("CLV_WGRAD_GROUP_ROWS")) : 0;
-    if (env_target > 0) target = env_target;
+    int64_t target = (cls ? WG_BIG_GROUP_TARGET : WG_GROUP_TARGET) / (n > 0 ? n : 1);
+    if (target < (cls ? WG_BIG_TARGET_MIN : WG_TARGET_MIN)) target = cls ? WG_BIG_TARGET_MIN : WG_TARGET_MIN;
+    if (cls && target > WG_BIG_TARGET_MAX) target = WG_BIG_TARGET_MAX;
     int64_t s = (target + tiles - 1) / tiles;
-    if (env_rows > 0) s = (M + env_rows - 1) / env_rows;
-    const int64_t max_by_rows = (M + 255) / 256;
+    const int64_t max_by_rows = (M + WG_MIN_SLICE_ROWS - 1) / WG_MIN_SLICE_ROWS;
     if (s > max_by_rows) s = max_by_rows;
     if (s < 1) s = 1;
     return (int)s;
@@ -1229,19 +978,14 @@ static int group_splits(int64_t M, int tiles, int n, int cls = 0) {
 // for outputs that such tiles cover without overhang; everything else keeps 128 x 128 tiles — with overhang the wide
 // tiles spend 30-80 % more MFMA / LDS time on clamped columns, and the compute side alone (479 us of the 760 us launch)
 // then exceeds what the DMA side saves (measured: 813 us with every shape that staged >= 20 % fewer bytes on wide tiles).
+// Few-row problems keep 128 x 128 tiles (A/B: 0.05 ms better).  128 x 256 / 256 x 128 classes were measured and dropped
+// (+0.25 ms on the step: two more launches, one 8-wave workgroup per CU).
 static int wg_class(int N, int K, int64_t M = 1 << 20) {
-    static const int big = getenv("CLV_WGRAD_BIG") ? atoi(getenv("CLV_WGRAD_BIG")) : 1;
-    static const int small_m = getenv("CLV_WGRAD_BIG_SMALLM") ? atoi(getenv("CLV_WGRAD_BIG_SMALLM")) : 0;   // few-row problems: 128 x 128 tiles (A/B: 0.05 ms better)
-    static const int rect = getenv("CLV_WGRAD_RECT") ? atoi(getenv("CLV_WGRAD_RECT")) : 0;   // probe: 128 x 256 / 256 x 128 classes (+0.25 ms on the step: two more launches, one 8-wave workgroup per CU)
-    if (M <= 1024 && !small_m) return 0;
-    if (!big) return 0;
-    if (N % 256 == 0 && K % 256 == 0) return 1;
-    if (rect && N % 128 == 0 && K % 256 == 0) return 2;      // 128 x 256 tiles, 8 waves
-    if (rect && N % 256 == 0 && K % 128 == 0) return 3;      // 256 x 128
-    return 0;
+    if (M <= 1024) return 0;
+    return (N % 256 == 0 && K % 256 == 0) ? 1 : 0;
 }
-constexpr int WG_CLASSES = 4;                               // the fixed-tile classes
-static const int wg_tn[WG_CLASSES] = {128, 256, 128, 256}, wg_tk[WG_CLASSES] = {128, 256, 256, 128};
+constexpr int WG_CLASSES = 2;                               // the fixed-tile classes
+static const int wg_tn[WG_CLASSES] = {128, 256}, wg_tk[WG_CLASSES] = {128, 256};
 // One M-slice accumulated straight into dW / db (no partials, no fold): few rows, or an output so large that every extra
 // slice costs more partial traffic (write + fold read of N x K floats) than it saves in workgroup length.
 static bool wg_in_place(int64_t M, int N, int K) {
@@ -1255,7 +999,7 @@ static int wg_tiles(int N, int K, int cls) {
 
 extern "C" int clv_linear_wgrad_batch_plan(ClvWgradEntry* entries, int32_t n) {
     if (!entries || n <= 0 || n > WG_GROUP_MAX) return CLV_ERR_ARG;
-    int ncls[WG_CLASSES] = {0, 0, 0, 0};
+    int ncls[WG_CLASSES] = {0, 0};
     for (int i = 0; i < n; ++i) {
         const ClvWgradEntry& e = entries[i];
         if (e.M <= 0 || e.N <= 0 || e.K <= 0 || (e.N & 7) || (e.K & 7)) return CLV_ERR_ARG;
@@ -1287,12 +1031,10 @@ extern "C" int clv_linear_wgrad_batch_ss(const ClvWgradEntry* entries, int32_t n
     // its ~260 workgroups used to run on alone after everything else had drained.
     int order[WG_GROUP_MAX];
     for (int i = 0; i < n; ++i) order[i] = i;
-    static const bool lpt = !getenv("CLV_WGRAD_LPT") || atoi(getenv("CLV_WGRAD_LPT")) != 0;
-    if (lpt)
-        std::stable_sort(order, order + n, [&](int a, int b) {
-            return entries[a].M / (entries[a].splits > 0 ? entries[a].splits : 1) >
-                   entries[b].M / (entries[b].splits > 0 ? entries[b].splits : 1);
-        });
+    std::stable_sort(order, order + n, [&](int a, int b) {
+        return entries[a].M / (entries[a].splits > 0 ? entries[a].splits : 1) >
+               entries[b].M / (entries[b].splits > 0 ? entries[b].splits : 1);
+    });
     for (int cls = 0; cls < WG_CLASSES; ++cls) {
         WgGroup grp;
         int blocks = 0, rot = 0, cnt = 0;
@@ -1334,28 +1076,15 @@ extern "C" int clv_linear_wgrad_batch_ss(const ClvWgradEntry* entries, int32_t n
         grp.n = cnt;
         grp.ssq = sumsq_slots;
         if (cls == 0) {
-            hipLaunchKernelGGL(wgrad_dma2_group_kernel, dim3((unsigned)blocks), dim3(wg_threads()), 0, (hipStream_t)stream,
+            hipLaunchKernelGGL(wgrad_dma2_group_kernel, dim3((unsigned)blocks), dim3(WG_THREADS), 0, (hipStream_t)stream,
                                grp);
-        } else if (cls == 1) {
-            constexpr int LDS = BIG_RING * 4 * 8192;
+        } else {
+            constexpr int LDS = BIG_RING * 4 * 8192;          // above 64 KB: opted into once per process
             static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_big_group_kernel<2, 2>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-            (void)attr;
+            if (!attr) return CLV_ERR_LAUNCH;
             hipLaunchKernelGGL((wgrad_big_group_kernel<2, 2>), dim3((unsigned)blocks), dim3(1024), LDS,
                                (hipStream_t)stream, grp);
-        } else {
-            constexpr int LDS = BIG_RING * 3 * 8192;
-            static const bool attr12 = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_big_group_kernel<1, 2>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-            static const bool attr21 = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_big_group_kernel<2, 1>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-            (void)attr12; (void)attr21;
-            if (cls == 2)
-                hipLaunchKernelGGL((wgrad_big_group_kernel<1, 2>), dim3((unsigned)blocks), dim3(512), LDS,
-                                   (hipStream_t)stream, grp);
-            else
-                hipLaunchKernelGGL((wgrad_big_group_kernel<2, 1>), dim3((unsigned)blocks), dim3(512), LDS,
-                                   (hipStream_t)stream, grp);
         }
         const int rc = clv_check_launch();
         if (rc) return rc;

@@ -541,11 +541,6 @@ __global__ void __launch_bounds__(256) ns_norm_bwd_kernel(NsWork W, float* d0, f
     for (int c = lane; c < Dm; c += 64) d[c] = clamped ? de[c] * -inv : inv * (de[c] - en[c] * s);
 }
 
-bool focal_wide() {
-    static const bool on = !(getenv("CLV_FOCAL_WIDE") && atoi(getenv("CLV_FOCAL_WIDE")) == 0);   // probe switch
-    return on;
-}
-
 }  // namespace
 
 static int focal_fwd_impl(const void* logits, int32_t is_bf16, const int64_t* labels, float* row_ce, float* row_lse,
@@ -554,7 +549,7 @@ static int focal_fwd_impl(const void* logits, int32_t is_bf16, const int64_t* la
     hipStream_t st = (hipStream_t)stream;
     // (loss, count) double as the {sum, count} accumulators (caller zeroes both); normalised in place
     // by the finish kernel
-    if (focal_wide() && is_bf16 && !(V & 1) && !(ld & 1) && !(reinterpret_cast<uintptr_t>(logits) & 3))
+    if (is_bf16 && !(V & 1) && !(ld & 1) && !(reinterpret_cast<uintptr_t>(logits) & 3))
         hipLaunchKernelGGL(focal_fwd_pairs_kernel, dim3((unsigned)rows), dim3(FC_WIDE), 0, st, (const unsigned*)logits,
                            labels, row_ce, row_lse, loss, count, (int)V, ld, gamma);
     else if (is_bf16)
@@ -575,7 +570,7 @@ static int focal_bwd_impl(const void* logits, int32_t is_bf16, const int64_t* la
     if (!logits || !labels || !row_ce || !row_lse || !count || !dloss || !dlogits || rows <= 0 || V <= 0 || ld < V)
         return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (focal_wide() && is_bf16 && !(V & 1) && !(ld & 1) &&
+    if (is_bf16 && !(V & 1) && !(ld & 1) &&
         !((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 3))
         hipLaunchKernelGGL(focal_bwd_pairs_kernel, dim3((unsigned)rows), dim3(FC_WIDE), 0, st, (const unsigned*)logits,
                            labels, row_ce, row_lse, count, dloss, (unsigned*)dlogits, (int)V, ld, gamma);

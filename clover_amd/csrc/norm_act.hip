@@ -8,6 +8,12 @@ namespace {
 
 constexpr int LN_THREADS = 256;
 constexpr int LN_WAVES = LN_THREADS / 64;
+// ---- host-side grid caps (re-tune by editing and A/B-ing two libraries through CLOVER_LIB_PATH); see lnv_blocks / ew_blocks
+constexpr int LN_GRID = 2048;             // row-per-wave LayerNorm kernels
+constexpr int LNV_FWD_GRID = 1 << 20;     // vector LayerNorm forward: one pass per wave (-0.08 ms)
+constexpr int LNV_GRID = 0;               // vector LayerNorm backward, one chunk per lane: 0 = every workgroup resident (3 or 5 per CU)
+constexpr int LNV_GRID2 = 512;            // ... two or more chunks per lane
+constexpr int EW_GRID = 1 << 20;          // element-wise kernels: one 16-byte group per thread: -0.14 ms per step vs 2048 grid-stride blocks
 
 // element pair load/store for the two I/O types (bf16 storage or fp32 storage)
 template <typename T> struct IO;
@@ -232,14 +238,9 @@ int ln_iters(int C) {
     return -1;
 }
 
-static int env_cap(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 int ln_fwd_blocks(int64_t rows) {
-    static const int cap = env_cap("CLV_LN_GRID", 2048);
     int64_t b = (rows + LN_WAVES - 1) / LN_WAVES;
-    if (b > cap) b = cap;
+    if (b > LN_GRID) b = LN_GRID;
     if (b < 1) b = 1;
     return (int)b;
 }
@@ -725,13 +726,11 @@ inline int lnv_blocks(int64_t rows, int group, bool fwd = false, int iters = 1) 
     // number of rows: 2 048 ran as one full round plus a 60 % one (round 4, same box: 11.99 -> 11.84 ms per step; 1 024, 1 536,
     // 2 560: 11.98, 12.14, 12.08)
     // (since the one-chunk kernels keep three row groups in flight at 3 waves per SIMD: 768 resident workgroups)
-    static const int cap_b = env_cap("CLV_LNV_GRID", 0), cap_f = env_cap("CLV_LNV_FWD_GRID", 1 << 20);
     // rows wider than 512 elements (two+ chunks per lane: C = 768 of stage 3 / the fusion encoder, 3 136-3 648 rows): 512
     // blocks of ~2 rows per wave write half the dgamma / dbeta partial rows of 912 one-row-per-wave blocks (5.6 MB beside 22 MB
     // of operands): 11.39 -> 11.36 ms per step, twice; 256: 11.47
-    static const int cap_b2 = env_cap("CLV_LNV_GRID2", 512);
     // one chunk per lane: every workgroup resident — 3 per CU where three row groups are in flight, else 5
-    const int cap = fwd ? cap_f : (iters > 1 ? cap_b2 : (cap_b > 0 ? cap_b : (group <= 32 && LNV_BWD_RG2 > 1 ? LNV_BWD_WAVES : 5) * 256));
+    const int cap = fwd ? LNV_FWD_GRID : (iters > 1 ? LNV_GRID2 : (LNV_GRID > 0 ? LNV_GRID : (group <= 32 && LNV_BWD_RG2 > 1 ? LNV_BWD_WAVES : 5) * 256));
     int64_t b = (rows + rpb - 1) / rpb;
     if (b > cap) b = cap;
     if (b < 1) b = 1;
@@ -820,9 +819,8 @@ __global__ void gelu_bwd_f32_kernel(const float* __restrict__ dy, const float* _
 }
 
 int ew_blocks(int64_t n8) {
-    static const int cap = env_cap("CLV_EW_GRID", 1 << 20);   // one 16-byte group per thread: -0.14 ms per step vs 2048 grid-stride blocks
     int64_t b = (n8 + 255) / 256;
-    if (b > cap) b = cap;
+    if (b > EW_GRID) b = EW_GRID;
     if (b < 1) b = 1;
     return (int)b;
 }

@@ -6,6 +6,8 @@
 
 namespace {
 
+constexpr int SUMSQ_GRID = 2048;          // host: workgroups of a sum-of-squares pass at most
+
 // Gradient element type of the optimizer kernels: fp32 (the slabs the backward accumulates into) or bf16 (the wire copy
 // a data-parallel job all-reduces over xGMI — half the bytes; the update itself stays fp32: clv_pack_bf16,
 // clv_sumsq_bf16, clv_adamw_step_dev_bf16g).
@@ -258,8 +260,7 @@ extern "C" int clv_sumsq(const float* g, float* acc, int64_t n, void* stream) {
     if (!g || !acc || n < 0) return CLV_ERR_ARG;
     if (n == 0) return CLV_OK;
     if (((uintptr_t)g) & 15) return CLV_ERR_ARG;
-    static const int sumsq_cap = getenv("CLV_SUMSQ_GRID") ? atoi(getenv("CLV_SUMSQ_GRID")) : 2048;
-    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid_for(n / 4, sumsq_cap)), dim3(256), 0, (hipStream_t)stream, g, acc, n);
+    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid_for(n / 4, SUMSQ_GRID)), dim3(256), 0, (hipStream_t)stream, g, acc, n);
     return clv_check_launch();
 }
 
@@ -267,7 +268,7 @@ extern "C" int clv_sumsq_bf16(const void* g, float* acc, int64_t n, void* stream
     if (!g || !acc || n < 0) return CLV_ERR_ARG;
     if (n == 0) return CLV_OK;
     if (((uintptr_t)g) & 7) return CLV_ERR_ARG;
-    hipLaunchKernelGGL(sumsq_kernel<bf16_t>, dim3(grid_for(n / 4, 2048)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(sumsq_kernel<bf16_t>, dim3(grid_for(n / 4, SUMSQ_GRID)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)g, acc, n);
     return clv_check_launch();
 }

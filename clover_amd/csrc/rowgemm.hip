@@ -19,6 +19,10 @@ namespace {
 
 constexpr int RG_THREADS = 256;
 constexpr int RG_WAVES = 4;
+// ---- host-side tuning numbers (re-tune by editing and A/B-ing two libraries through CLOVER_LIB_PATH)
+constexpr int RG_BIG_TILE_WAVES = 8;      // waves that share a weight tile of >= 48 KB at least (twelve where K <= 256 and LDS allows)
+constexpr int RG_SMALL_K_WAVES = 8;       // waves per workgroup of the K <= 128 GELU' / LayerNorm-prologue variants (4: the plain launch)
+constexpr int RG_ROW_SLICE_MULT = 1;      // finer row slices: measured, no gain
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GELU_BWD = 2 };
 
@@ -215,7 +219,7 @@ int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float*
     // a weight tile of >= 64 KB leaves ONE workgroup per CU: eight waves share it instead of four (K = 288 / 384: the
     // stage-0 qkv input gradient and fc2)
     if constexpr (NW == RG_WAVES && KS >= 6 && KS <= 12) {
-        static const int wv = getenv("CLV_RG_WAVES") ? atoi(getenv("CLV_RG_WAVES")) : 8;
+        constexpr int wv = RG_BIG_TILE_WAVES;
         const size_t wbytes = (size_t)C::TN * C::LDW * 2 + (size_t)C::TN * 4, per_wave = (size_t)NST * 16 * C::LDO * 2;
         if (wbytes >= 48 * 1024) {
             if ((wv == 12 || (KS <= 8 && wv >= 8)) && wbytes + 12 * per_wave <= 160 * 1024)
@@ -230,8 +234,7 @@ int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float*
     // workgroups put 24 waves on a CU where five 4-wave ones (LDS) put 20 — 108 -> 91 us for the former.  The prologue
     // variants fit the 80 VGPRs that 24 waves allow since the bias row moved to LDS (K = 96: 76-78; K = 128 spills: 4 waves).
     if constexpr (NW == RG_WAVES && ((KS <= 4 && !STD && EPI == EPI_GELU_BWD) || (KS <= 3 && STD))) {
-        static const int w3 = getenv("CLV_RG_WAVES3") ? atoi(getenv("CLV_RG_WAVES3")) : 8;
-        if (w3 == 8)
+        if (RG_SMALL_K_WAVES == 8)
             return launch_rg<KS, STD, EPI, 8>(x, res, sum_out, mean, rstd, xhat_out, wt, bias, pre_in, y, pre_out, M, N, ldx, ldy,
                                               eps, st, xscale, rps);
     }
@@ -255,8 +258,7 @@ int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float*
         gx = 1536 / ny;
         if (gx < 256) gx = 256;
     }
-    static const int mult = getenv("CLV_RG_MULT") ? atoi(getenv("CLV_RG_MULT")) : 1;   // probe: finer row slices
-    gx *= mult;
+    gx *= RG_ROW_SLICE_MULT;
     if (gx < 8) gx = 8;
     if (gx > row_blocks) gx = row_blocks;
     rowgemm_kernel<KS, STD, EPI, NW><<<dim3((unsigned)(gx * ny)), dim3(64 * NW), lds, st>>>(

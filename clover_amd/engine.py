@@ -422,24 +422,10 @@ class CloverEngine:
             ref = run([])
             log, ops.FRESH_LOG = ops.FRESH_LOG, None
             cand = [ptr for ptr, (calls, numel) in log.items() if calls == 1 and ptr in sinks and sinks[ptr][3] == numel]
-            dbg = os.environ.get('CLOVER_FT_DEBUG') == '1'
-            if dbg:
-                print(f'[first-touch] sinks {len(sinks)}  logged {len(log)}  candidates {len(cand)}', flush=True)
             # exactly three passes on every rank, whatever they find: the step contains collectives (feature all-gather)
             got = run(cand)
             ok = [ptr for ptr in cand if same(span(got, ptr), span(ref, ptr))]
-            if dbg:
-                bad = [ptr for ptr in cand if ptr not in ok]
-                print(f'[first-touch] pass {len(ok)}  fail {len(bad)}', flush=True)
-                for ptr in bad[:6]:
-                    a, r = span(got, ptr), span(ref, ptr)
-                    print('   fail numel', sinks[ptr][3], 'finite', bool(torch.isfinite(a).all()),
-                          'relerr', float((a - r).norm() / (r.norm() + 1e-30)), flush=True)
             got = run(ok)
-            if dbg:
-                for si, (g, r) in enumerate(zip(got, ref)):
-                    print(f'[first-touch] validation slab {si}: finite {bool(torch.isfinite(g).all())} relerr '
-                          f'{float((g - r).norm() / (r.norm() + 1e-30)):.3e}', flush=True)
             if not all(same(g, r) for g, r in zip(got, ref)):
                 ok = []
         finally:
@@ -562,7 +548,7 @@ class CloverEngine:
         """Run a backward pass / segment with the weight-gradient folds deferred to ONE batched launch at its end —
         unless gradient-ready hooks put buckets on the wire from inside the pass (eager data-parallel mode), where a
         gradient must be final when its hook fires."""
-        if (self.reducer.active and self.reducer.enabled) or os.environ.get('CLOVER_DEFER_FOLDS', '1') != '1':
+        if self.reducer.active and self.reducer.enabled:
             run()
         else:
             with ops.defer_folds():
@@ -727,8 +713,7 @@ class CloverEngine:
         import inspect
         cut_ok = self.reducer.active and hasattr(model, 'backbone')
         text_ok = (cut_ok and hasattr(model, 'text_backbone')
-                   and 'text_cut' in inspect.signature(model.encode).parameters
-                   and os.environ.get('CLOVER_TEXT_CUT', '1') == '1')
+                   and 'text_cut' in inspect.signature(model.encode).parameters)
         if text_ok and getattr(self, '_bwd_text_stream', None) is None:
             self._bwd_text_stream = torch.cuda.Stream()
 
@@ -786,7 +771,7 @@ class CloverEngine:
         self._static_dmlm = torch.zeros_like(mlm) if mlm is not None else None
         # Data-parallel jobs: the bf16 wire copy of every bucket is written INSIDE the backward graph that completes its
         # gradients (the pack kernels are plain launches; only the RCCL calls stay between the replays)
-        pack = cut_ok and os.environ.get('CLOVER_PACK_IN_GRAPH', '1') == '1'
+        pack = cut_ok
         prepacked = set()
         with torch.cuda.graph(gb, pool=gf.pool(), capture_error_mode='thread_local'):
             self._backward(lambda: torch.autograd.backward(*roots(emb, mlm, self._static_demb, self._static_dmlm)))

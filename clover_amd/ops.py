@@ -34,8 +34,9 @@ LIBRARY_GEMM_CALLS = {}     # {(site, shape): calls} of every GEMM that left the
 
 
 def _library_gemm(site, shape):
-    """Every GEMM of the Clover configs runs on the own kernels; a shape they do not take (a contraction that is not a
-    multiple of 64, a sequence beyond 896 keys, ...) falls back to the ROCm library THROUGH HERE: counted in
+    """Every GEMM of the Clover configs runs on the own kernels, and no switch routes one elsewhere; only a shape they do
+    not take (a contraction that is not a multiple of 64 such as the 48-wide tiny model, a sequence beyond 896 keys, ...)
+    goes to the ROCm library, and only THROUGH HERE: counted in
     LIBRARY_GEMM_CALLS (bench.py prints the table, the step tests assert it stays empty), announced once per shape, and
     refused with CLOVER_STRICT_OWN_GEMM=1 — never silent."""
     key = (site, tuple(int(v) for v in shape))
@@ -223,17 +224,9 @@ def roofline_from_prof(prof, steps):
 def _wgrad_custom(M, N, K):
     """Shapes the split-M weight-gradient kernels take: every Linear whose widths are multiples of 8 (16-byte row groups)
     — token-parallel ones (huge M, small N x K), few-row ones (M <= 1024: one M-slice accumulated straight into the fp32
-    gradient), the 256 x 256-tile class for the large stage-3 / fusion outputs, and (round 6) what used to fall between
-    them: 1024 < M < 2048 rows (Swin stage 3 / the fusion encoder at per-GPU batch 1-4) and M >= 2048 with an output
-    beyond 2^20 elements whose widths are not multiples of 256 — M-slices of >= 256 rows on the 128 x 128 tiles.
-    CLOVER_WGRAD_HOLE=1 restores the rounds-1-5 dispatch (those shapes on the library GEMM) for A/B runs."""
-    if N % 8 or K % 8:
-        return False
-    if os.environ.get('CLOVER_WGRAD_HOLE', '0') != '1':
-        return True
-    if M >= 2048 and N % 256 == 0 and K % 256 == 0 and os.environ.get('CLOVER_WGRAD_WIDE', '1') == '1':
-        return True                        # 256 x 256 tiles in the grouped launch: also the large stage-3 / fusion outputs
-    return M >= 2048 and N * K <= (1 << 20) or M <= 1024
+    gradient), the 256 x 256-tile class for the large stage-3 / fusion outputs, and everything between them on M-slices
+    of >= 256 rows of the 128 x 128 tiles."""
+    return N % 8 == 0 and K % 8 == 0
 
 
 FRESH_LOG = None            # census (engine set-up): {data_ptr: [calls, numel]} of every sink linear_wgrad writes
@@ -365,9 +358,9 @@ class defer_folds:
 
     def __enter__(self):
         global FOLD_DEFER, LN_DEFER, WGRAD_DEFER, POST_DEFER, DBIAS_DEFER
-        self.prev_db, DBIAS_DEFER = DBIAS_DEFER, ([] if os.environ.get('CLOVER_DEFER_DBIAS', '1') == '1' else None)
+        self.prev_db, DBIAS_DEFER = DBIAS_DEFER, []
         self.prev, FOLD_DEFER = FOLD_DEFER, []
-        self.prev_ln, LN_DEFER = LN_DEFER, ([] if os.environ.get('CLOVER_DEFER_LN', '1') == '1' else None)
+        self.prev_ln, LN_DEFER = LN_DEFER, []
         self.prev_wg, WGRAD_DEFER = WGRAD_DEFER, ([] if os.environ.get('CLOVER_GROUP_WGRAD', '1') == '1' else None)
         self.prev_post, POST_DEFER = POST_DEFER, []
         return self
@@ -379,93 +372,53 @@ class defer_folds:
         pending_ln, LN_DEFER = LN_DEFER, self.prev_ln
         pending_wg, WGRAD_DEFER = WGRAD_DEFER, self.prev_wg
         pending_post, POST_DEFER = POST_DEFER, self.prev_post
-        if exc[0] is None:
-            join_aux_streams()
+        if exc[0] is None:                 # (a backward segment that raised launches nothing that it deferred)
             pending = pending + flush_wgrads(pending_wg or [])
             flush_folds(pending)
             for fn in pending_post:
                 fn()
-            flush_ln_reduces(pending_ln or [])
-            flush_dbias_gathers(pending_db or [])
-        else:
-            # a backward segment that raised: nothing deferred is launched, but whatever already runs on an auxiliary stream
-            # is joined and its operands released — _AUX_HOLD must not carry entries into the next segment
-            join_aux_streams()
+            flush_ln_reduces(pending_ln)
+            flush_dbias_gathers(pending_db)
         return False
 
 
-_AUX_STREAMS = {}           # device index -> auxiliary stream of flush_stream_wgrads(aux=True)
-_AUX_HOLD = []              # (stream, flushed items, their fold entries): alive until the calling stream has joined it
-
-
-def flush_stream_wgrads(aux=False):
-    """Launch NOW the deferred weight gradients that were queued from the current stream (and the folds of their
-    partials), leaving the others pending.
-    aux=False: on the current stream.  The text tower's backward runs on a side stream beside the video tower's: at its end
-    (`flush_point` on the embedding output) its 48 few-row weight gradients go out there, under the rest of the video
-    backward, instead of as the last grouped launch of the step on the main stream.
-    aux=True: on an auxiliary stream that forks from the current one here and is joined when the backward segment closes
-    (`join_aux_streams`): the heads' / fusion encoder's weight gradients, complete when the fusion backward ends, run under
-    the video tower's backward.  Everything they read or write stays referenced until the join."""
+def flush_stream_wgrads():
+    """Launch NOW, on the current stream, the deferred weight gradients that were queued from it (and the folds of their
+    partials), leaving the others pending.  The text tower's backward runs on a side stream beside the video tower's: at
+    its end (`flush_point` on the embedding output) its 48 few-row weight gradients go out there, under the rest of the
+    video backward, instead of as the last grouped launch of the step on the main stream.
+    (The same for the heads' / fusion encoder's gradients on an auxiliary stream was measured and dropped: same-box
+    11.09 / 11.16 -> 11.28 / 11.33 ms — MFMA-heavy grouped launches beside the video chain take the CUs and the HBM that
+    chain is bound by, as the early video launches of round 4 did.)"""
     global WGRAD_DEFER
     if WGRAD_DEFER is None or not WGRAD_DEFER:
         return
-    cur_s = torch.cuda.current_stream()
-    cur = cur_s.cuda_stream
+    cur = torch.cuda.current_stream().cuda_stream
     mine = [it for it in WGRAD_DEFER if len(it) > 8 and it[8] == cur]
     if not mine:
         return
     WGRAD_DEFER[:] = [it for it in WGRAD_DEFER if not (len(it) > 8 and it[8] == cur)]
-    if not aux:
-        folds = flush_wgrads(mine)
-        if folds:
-            flush_folds(folds)
-        return
-    dev = mine[0][0].device
-    st = _AUX_STREAMS.get(dev.index)
-    if st is None:
-        st = _AUX_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
-    st.wait_stream(cur_s)
-    with torch.cuda.stream(st):
-        folds = flush_wgrads(mine)
-        if folds:
-            flush_folds(folds)
-    _AUX_HOLD.append((st, mine, folds))
-
-
-def join_aux_streams():
-    """The current stream waits for every auxiliary flush of this backward segment; their operands may be released then."""
-    if _AUX_HOLD:
-        cur = torch.cuda.current_stream()
-        for st, _, _ in _AUX_HOLD:
-            cur.wait_stream(st)
-        del _AUX_HOLD[:]
+    folds = flush_wgrads(mine)
+    if folds:
+        flush_folds(folds)
 
 
 class _FlushPoint(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, aux):
-        ctx.aux = aux
+    def forward(ctx, x):
         return x.view_as(x)
 
     @staticmethod
     def backward(ctx, g):
-        flush_stream_wgrads(ctx.aux)
-        return g, None
+        flush_stream_wgrads()
+        return g
 
 
-def flush_point(x, aux=False):
+def flush_point(x):
     """Identity whose backward flushes the deferred weight gradients of the stream it runs on (see flush_stream_wgrads)."""
-    on = WGRAD_FLUSH_AUX if aux else WGRAD_FLUSH_POINTS
-    if on and x.requires_grad and x.is_cuda:
-        return _FlushPoint.apply(x, bool(aux))
+    if x.requires_grad and x.is_cuda:
+        return _FlushPoint.apply(x)
     return x
-
-
-# (off by default: same-box 11.09 / 11.16 -> 11.28 / 11.33 ms — MFMA-heavy grouped launches beside the video chain take
-# the CUs and the HBM that chain is bound by, as the early video launches of round 4 did)
-WGRAD_FLUSH_AUX = os.environ.get('CLOVER_FUSION_WGRAD_AUX', '0') == '1'
-WGRAD_FLUSH_POINTS = os.environ.get('CLOVER_TEXT_WGRAD_SIDE', '1') == '1'
 
 
 def wgrad_chunks(pending):
@@ -493,9 +446,6 @@ def flush_wgrads(pending):
     folds = []
     L = _lib.lib()
     for chunk in wgrad_chunks(pending):
-        if os.environ.get('CLOVER_WGRAD_LOG') == '1':       # probe: the (M, N, K) of every grouped launch
-            print('WGRAD_GROUP', len(chunk), sorted({(c[4], c[5], c[6]): 0 for c in chunk}.keys()),
-                  [(c[4], c[5], c[6]) for c in chunk], flush=True)
         arr = (_lib.ClvWgradEntry * len(chunk))()
         for e, (dy2, x2, dw, db, M, N, K, *_) in zip(arr, chunk):
             e.dy, e.x, e.M, e.N, e.K = dy2.data_ptr(), x2.data_ptr(), M, N, K
@@ -519,8 +469,7 @@ def flush_wgrads(pending):
         if PROF is None:
             check(L.clv_linear_wgrad_batch_ss(arr, len(chunk), _ptr(slots), _stream()), 'clv_linear_wgrad_batch')
         else:                                        # one event pair per device kernel: the tile classes one by one
-            for cls, kname in ((0, 'wgrad_dma2_group_kernel'), (1, 'wgrad_big_group_kernel<2, 2>'),
-                               (2, 'wgrad_big_group_kernel<1, 2>'), (3, 'wgrad_big_group_kernel<2, 1>')):
+            for cls, kname in ((0, 'wgrad_dma2_group_kernel'), (1, 'wgrad_big_group_kernel<2, 2>')):
                 sub = [e for e in arr if L.clv_linear_wgrad_class(e.M, e.N, e.K) == cls]
                 if not sub:
                     continue
@@ -594,13 +543,6 @@ def _rowgemm_fwd_ok(x, N, K):
     return x.is_cuda and K <= 128 and x.stride(-1) == 1 and rowgemm_supported(N, K)
 
 
-def own_gemm_all():
-    """CLOVER_OWN_GEMM_ALL=1 (default): every forward / input-gradient GEMM of a Linear whose shape clv_gemm_nt takes
-    runs on it — Swin stages 1-3, PatchMerging, the text tower, the fusion encoder, fc_in, the MLM transform (round 3;
-    the MLM decoder, N = 30522, stays a library GEMM).  0: only where it beat the tuned library GEMM in round 2."""
-    return os.environ.get('CLOVER_OWN_GEMM_ALL', '1') == '1'
-
-
 # Widest output clv_gemm_nt is handed by the Linear wrappers.  Up to 3072 columns the bias row sits in LDS; wider outputs
 # (VideoSwin-B's stage-3 MLP: 4096; round 6 — they used to fall to the library) read it from global memory in the epilogue,
 # as the MLM decoder's 30 528 columns always did.
@@ -609,27 +551,21 @@ OWN_GEMM_MAX_N = 65536
 
 def own_gemm_ok(a, N, K):
     """Shapes that run on clv_gemm_nt (forward: a = x [M, K], N outputs; input gradient: a = dy, contraction = the layer's
-    output width).  Device-side durations against the tuned library GEMM: tools/probes/gemm_bench.py (round 2: token-
-    parallel layers with a short contraction win) and tools/probes/gemm_tiles.py (round 3: the 64 x 128 tile class for
-    long contractions with few tiles)."""
-    M = a.shape[0]
-    if not (os.environ.get('CLOVER_OWN_GEMM', '1') == '1' and a.is_cuda and a.dtype == BF16 and K % 64 == 0 and K >= 64
+    output width): every forward / input-gradient GEMM of a Linear whose shape the kernel takes — Swin stages 1-3,
+    PatchMerging, the text tower, the fusion encoder, fc_in, the MLM transform — from one row up (a 3-caption
+    text batch has 48).  Device-side durations against the tuned library GEMM: tools/probes/gemm_bench.py and
+    tools/probes/gemm_tiles.py."""
+    return (a.is_cuda and a.dtype == BF16 and a.shape[0] >= 1 and K % 64 == 0 and K >= 64
             and 64 <= N <= OWN_GEMM_MAX_N and N % 8 == 0 and a.stride(1) == 1 and a.stride(0) % 8 == 0
-            and a.data_ptr() % 16 == 0):
-        return False
-    if own_gemm_all():
-        return M >= 1          # (round 6: few-row calls — a 3-caption text batch, 48 rows — used to leave for the library below 64)
-    return M >= 8192 and K <= 576
+            and a.data_ptr() % 16 == 0)
 
 
 def wants_transposed(out_features, in_features):
     """Does the input gradient of a Linear(in, out) run on a kernel that takes W^T as a K-contiguous operand
     (linear_dgrad: the row-streaming GEMM of the stage-0 widths, clv_gemm_nt otherwise)?  Modules flag such weights
     (``_clv_want_t``) and the engine keeps their bf16 transposes fresh."""
-    if own_gemm_all():
-        return (out_features % 64 == 0 and 64 <= in_features <= OWN_GEMM_MAX_N and in_features % 8 == 0) or \
-               (in_features <= 128 and out_features <= 384)
-    return out_features <= 576 or (in_features <= 128 and out_features <= 384)
+    return (out_features % 64 == 0 and 64 <= in_features <= OWN_GEMM_MAX_N and in_features % 8 == 0) or \
+           (in_features <= 128 and out_features <= 384)
 
 
 # --------------------------------------------------------------------------- fp8 forward GEMMs (BASELINE config 5)
@@ -694,11 +630,12 @@ def _wt(weight, wb):
 def linear_dgrad(dy2, wb, weight=None, pre=None):
     """dx [M,K] = dy [M,N] . W [N,K] (pre: times GELU'(pre), the fc2 input gradient of an MLP): as a row-streaming GEMM
     over the contraction N when that is short (<= 288) or the output is narrow (K <= 128); the LDS-tiled HIP GEMM with
-    W^T as its K-contiguous B operand where that wins (own_gemm_ok); the library GEMM otherwise."""
+    W^T as its K-contiguous B operand for every other shape it takes (own_gemm_ok), with GELU' fused into its epilogue;
+    a shape outside both goes through _library_gemm."""
     N, K = wb.shape
     if pre is None and dy2.is_cuda and (N <= 288 or K <= 128 and N <= 384) and rowgemm_supported(K, N) and dy2.stride(1) == 1:
         return rowgemm(dy2, _wt(weight, wb), None)['y']
-    if own_gemm_ok(dy2, K, N) and (pre is None or os.environ.get('CLOVER_DGELU_FUSE', '1') == '1'):
+    if own_gemm_ok(dy2, K, N):
         return gemm_nt(dy2, _wt(weight, wb), aux=pre, epilogue=GEMM_EPI_DGELU if pre is not None else GEMM_EPI_NONE)
     _library_gemm('linear_dgrad', (dy2.shape[0], K, N))
     dx = torch.mm(dy2, wb)
@@ -954,7 +891,6 @@ def _wgrad_folded(dy2, xhat, xs, mean, rstd, weight, bias, gamma, beta):
     temporary), the un-fold kernel runs after the folds."""
     ps = (weight, bias, gamma, beta)
     if (WGRAD_DEFER is not None and POST_DEFER is not None and xhat is not None
-            and os.environ.get('CLOVER_DEFER_UNFOLD', '1') == '1'
             and all(getattr(q, '_clv_grad', None) is not None and q._clv_grad.dtype == torch.float32
                     for q in ps if q is not None)):
         (M, N), K = dy2.shape, xhat.shape[1]
@@ -1111,8 +1047,7 @@ class _FusedMLP(torch.autograd.Function):
             b2b = getattr(b2, '_clv_shadow', None)
             if b2b is None:
                 b2b = b2.to(BF16)
-        if own_gemm_ok(o1['y'], w2b.shape[0], w2b.shape[1]) and os.environ.get('CLOVER_FC2_OWN', '1') == '1':
-            # fc2 of the stage-0 block (200 704 x 96 x 384): the last library GEMM of the video tower
+        if own_gemm_ok(o1['y'], w2b.shape[0], w2b.shape[1]):     # fc2 of the stage-0 block (200 704 x 96 x 384)
             out = gemm_nt(o1['y'], w2b, b2.detach() if b2 is not None else None,
                           epilogue=GEMM_EPI_BIAS if b2 is not None else GEMM_EPI_NONE)
         else:
@@ -1249,8 +1184,7 @@ class _MlpGelu(torch.autograd.Function):
         # the second output is GELU'(pre) rather than pre when fc2's input gradient runs on clv_gemm_nt too: its
         # epilogue then is one multiply per element (no erf / exp in the backward)
         Hd, C_ = w1b.shape[0], w2b.shape[0]
-        ctx.dgelu_saved = (os.environ.get('CLOVER_GELU_SAVE_GRAD', '1') == '1' and own_gemm_ok(x2, Hd, C_)
-                           and os.environ.get('CLOVER_DGELU_FUSE', '1') == '1')
+        ctx.dgelu_saved = own_gemm_ok(x2, Hd, C_)
         if ctx.dgelu_saved and fp8_ok(x2, Hd, C_):
             act, pre = gemm_nt_fp8(x2, w1b, b1.detach(), epilogue=GEMM_EPI_BIAS_GELU_D, aq8=xq)
         else:
@@ -1307,12 +1241,11 @@ def _gemm_kname(M, N, K, epi, fp8, split=False):
     the same event bracket)."""
     t128 = ((M + 127) // 128) * ((N + 127) // 128)
     t64 = ((M + 63) // 64) * ((N + 127) // 128)
-    ws = 0 if fp8 else int(os.environ.get('CLV_GEMM_WS', '3'))
-    if (ws & 2) and M <= 1024 and K >= 512 and t64 <= 256 and N <= 3072:          # N <= GN_MAX_BIAS (gemm_nt.hip gn_plan)
+    if not fp8 and M <= 1024 and K >= 512 and t64 <= 256 and N <= 3072:          # N <= GN_MAX_BIAS (gemm_nt.hip gn_plan)
         return f"gemm_ws_kernel<64, 128, 2, 2, 2, 4, {6 if split else epi}>"
-    if (ws & 1) and t128 <= 256 and K >= 1536 and N <= 3072:
+    if not fp8 and t128 <= 256 and K >= 1536 and N <= 3072:
         return f"gemm_ws_kernel<128, 128, 2, 4, 2, 4, {6 if split else epi}>"
-    if not fp8 and os.environ.get('CLV_GEMM_T192', '1') != '0' and N % 192 == 0 and N <= 576 and M >= 8192:
+    if not fp8 and N % 192 == 0 and N <= 576 and M >= 8192:
         if ((M + 127) // 128) * (N // 192) <= 256:
             return f"gemm_nt_kernel<64, 192, 2, 2, 2, {epi}, false>"                     # 4 waves of 32 x 96, ring of 2
         return f"gemm_nt_kernel<128, 192, 4, 2, 3, {epi}, false>"                        # 8 waves of 32 x 96, ring of 3
@@ -1394,7 +1327,7 @@ def rowgemm(x, wt, bias=None, res=None, standardise=False, epilogue=0, pre_in=No
     rstd = torch.empty_like(mean) if standardise else None
     pre = torch.empty_like(y) if epilogue == 1 else None
     bf = _c(bias.float()) if bias is not None else None
-    xhat = torch.empty_like(x) if (want_xhat and standardise and os.environ.get('CLOVER_XHAT', '1') == '1') else None
+    xhat = torch.empty_like(x) if (want_xhat and standardise) else None
     if xscale is not None:
         check(_lib.lib().clv_rowgemm_xs(_ptr(x), _ptr(res), _ptr(ssum), _ptr(mean), _ptr(rstd), _ptr(xhat), _ptr(wt), _ptr(bf),
                                         _ptr(pre_in), _ptr(y), _ptr(pre), M, N, K, x.stride(0), N, int(bool(standardise)),
@@ -1422,7 +1355,7 @@ _LN_FP8_OUT = None          # side channel: the (q8, scale) pair the last _Layer
 def ln_emits_fp8(C_, f32):
     """CLOVER_FP8=1: LayerNorms whose width an fp8 GEMM can contract over also write their output as e4m3 + row scales
     (the activation operand of the QKV / FFN-in GEMM that follows: no separate quantisation pass over the activation)."""
-    return FP8 and not f32 and C_ % 128 == 0 and 256 <= C_ <= 3072 and os.environ.get('CLOVER_FP8_LN', '1') == '1'
+    return FP8 and not f32 and C_ % 128 == 0 and 256 <= C_ <= 3072
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -2229,7 +2162,7 @@ class _MLMDecoder(torch.autograd.Function):
 def mlm_decoder_ok(x, weight, bias):
     """The own-kernel decoder: engine-managed parameters bring their phantom-padded views; without an engine the padded
     operands are built per call (hidden width a multiple of 64: whole GEMM stages).  Not the parity path."""
-    if parity.enabled() or not x.is_cuda or bias is None or os.environ.get('CLOVER_OWN_DECODER', '1') != '1':
+    if parity.enabled() or not x.is_cuda or bias is None:
         return False
     if all(hasattr(weight, a) for a in ('_clv_pad_shadow', '_clv_pad_shadow_t', '_clv_pad_grad')):
         return hasattr(bias, '_clv_pad_weight') and hasattr(bias, '_clv_pad_grad')

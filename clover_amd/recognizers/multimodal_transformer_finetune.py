@@ -105,7 +105,7 @@ class CloverFinetune(BaseRecognizer):
         if vis.shape[0] != B:                                                         # :73-75 clip average
             vis = vis.reshape((B, -1) + vis.shape[1:]).float().mean(dim=1)
         _, T, hh, ww, Dv = vis.shape
-        fusion = self.multimodal_backbone(visual_token=ops.flush_point(vis.reshape(B, T, hh * ww, Dv), aux=True),
+        fusion = self.multimodal_backbone(visual_token=vis.reshape(B, T, hh * ww, Dv),
                                           text_input_mask=mask, text_input_embeds=text, num_choices=C,
                                           return_attention=test)
         h = fusion['last_hidden_state']

@@ -10,7 +10,6 @@ LayerNorm only — so batching passes along dim 0 changes no value):
   * MLM head only on the t_fusion half; all B*L rows go through the decoder and the fused
     focal kernel skips label == -100 rows (:134-139) — no data-dependent shapes, no host sync.
 """
-import os
 
 import torch
 
@@ -117,7 +116,7 @@ class CloverPretrain(BaseRecognizer):
                 text_out = self._cut(self.text_backbone(text_ids2, text_mask2)['last_hidden_state'], text_cut)
                 txt_emb_both = self.ssl_head.forward_text(text_out, passes=2, order=(1, 0), live=text_live)   # :150 / :102, also text-only
                 fusion_prep = None
-                if os.environ.get('CLOVER_HEADS_SIDE', '1') == '1' and hasattr(self.multimodal_backbone, 'prepare'):
+                if hasattr(self.multimodal_backbone, 'prepare'):
                     # the video-independent part of the fusion encoder's input (text + type embeddings, position table,
                     # key mask) here, behind the text encoder, not between the video encoder and the first fusion layer
                     mb = self.multimodal_backbone
@@ -148,7 +147,7 @@ class CloverPretrain(BaseRecognizer):
         # The vision projection head (pool + 2 Linear + 2 LayerNorm + GELU: ~10 launch-bound kernels) feeds only the loss:
         # it runs on the side stream under the fusion encoder (and, autograd replaying it there, its backward under the
         # fusion encoder's backward) instead of between the video encoder and the fusion encoder.
-        heads_side = side is not None and os.environ.get('CLOVER_HEADS_SIDE', '1') == '1'
+        heads_side = side is not None
         if heads_side:
             side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -164,9 +163,7 @@ class CloverPretrain(BaseRecognizer):
             for v_ in fusion_prep.values():
                 if torch.is_tensor(v_):
                     v_.record_stream(main)
-        # flush_point(aux): the fusion encoder's backward ends at its visual input — the weight gradients of the heads and of
-        # the fusion encoder, complete by then, leave on an auxiliary stream under the video tower's backward
-        fusion = self.multimodal_backbone(visual_token=ops.flush_point(vis_both.reshape(2 * B, T, h * w, D), aux=True),
+        fusion = self.multimodal_backbone(visual_token=vis_both.reshape(2 * B, T, h * w, D),
                                           text_input_mask=text_mask2, text_input_embeds=text_out,
                                           prepared=fusion_prep if side is not None else None)
         # row block 0 = t_fusion, block 1 = v_fusion: the caption tokens of block 0 feed the MLM decoder (:129), the caption
@@ -236,8 +233,7 @@ class CloverPretrain(BaseRecognizer):
              else gather_rows(emb.float(), equal_sizes=self.ssl_loss.equal_batch).contiguous())
         V, T, MW, MVR, MV, MWR = range(6)                      # EMB_NAMES order
         losses = dict(mlm_loss=mlm_loss) if mlm_loss is not None else {}
-        pair = (self.mlm_ssl_V_head is not None and self.symmetry_rank and g.is_cuda
-                and os.environ.get('CLOVER_LOSS_PAIR', '1') == '1')
+        pair = self.mlm_ssl_V_head is not None and self.symmetry_rank and g.is_cuda
         if pair:                                               # both evaluations in the same kernel launches
             l1, l2 = self.ssl_loss.forward_gathered_pair(g, (V, T, MW, MVR), (T, V, MV, MWR))              # :151, :161
             losses.update(l1)

@@ -13,7 +13,11 @@
  *   - bf16 tensors are `void*` (uint16 storage), row-major, innermost contiguous;
  *   - `stream` is a hipStream_t passed as void*; all calls are asynchronous on it,
  *     allocate nothing, and are capturable into a hipGraph;
- *   - return 0 on success, negative CLV_ERR_* otherwise; no exceptions.
+ *   - return 0 on success, negative CLV_ERR_* otherwise; no exceptions.  CLV_ERR_LAUNCH: a kernel launch, or the
+ *     once-per-process opt-in of a kernel to more than 64 KB of dynamic LDS, failed;
+ *   - the library reads three environment variables, each per call because tests flip them between two live paths:
+ *     CLV_ATTN_BWD_ONE, CLV_GEMM_SPLITK, CLV_GEMM_ROT.  Every other choice — tile classes,
+ *     grids, slice counts — is fixed at build time.
  */
 #ifndef CLOVER_HIP_H
 #define CLOVER_HIP_H

@@ -119,6 +119,55 @@ def test_c_abi_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.ClvLnExtra) == 80                   # ... + q8 / qscale pointers (round 3)
 
 
+def test_env_variable_census():
+    """The environment variables the product reads are exactly the table of INTEGRATION.md section 4: every name handed to
+    os.environ.get / os.environ[...] / os.getenv in clover_amd/**/*.py and to getenv (or the one helper around it,
+    clv_env_int) in clover_amd/csrc/*.{hip,hpp}.  CLV_GEMM_TILE is allowed only inside the #ifdef GN_LAB block of
+    gemm_nt.hip, which the shipped libraries do not compile."""
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    sect = doc[doc.index('## 4. Environment variables'):]
+    documented = set(re.findall(r'^\| `((?:CLOVER|CLV)_[A-Z0-9_]+)` \|', sect, re.M))
+    assert len(documented) == 19, sorted(documented)
+
+    read, env_calls = set(), 0
+    py_name = re.compile(r'''(?:os\.environ\.get\(|os\.environ\[|os\.getenv\(|environ\.get\(|getenv\()\s*(['"])([^'"]+)\1''')
+    for dirpath, _, files in os.walk(os.path.join(ROOT, 'clover_amd')):
+        for f in files:
+            if f.endswith('.py'):
+                src = open(os.path.join(dirpath, f)).read()
+                src = re.sub(r'^\s*#.*$', '', src, flags=re.M)
+                names = [m.group(2) for m in py_name.finditer(src)]
+                # every access to the environment names its variable literally, so none escapes the census
+                env_calls = len(re.findall(r'\benviron\b(?!\w)|\bgetenv\b', src))
+                assert env_calls == len(names), (f, env_calls, names)
+                read |= set(names)
+    csrc = os.path.join(ROOT, 'clover_amd', 'csrc')
+    c_name = re.compile(r'\b(?:getenv|clv_env_int)\s*\(\s*"([^"]+)"')
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(('.hip', '.hpp')):
+            continue
+        lab = 0
+        for line in open(os.path.join(csrc, f)):
+            s = line.strip()
+            if lab:                                             # inside #ifdef GN_LAB (the blocks hold no nested #if)
+                lab = 0 if s.startswith('#endif') else 1
+            elif s.startswith('#ifdef GN_LAB'):
+                lab = 1
+            code = line.split('//')[0]
+            for name in c_name.findall(code):
+                if name == 'CLV_GEMM_TILE':
+                    assert lab and f == 'gemm_nt.hip', (f, line)
+                else:
+                    assert not lab, (f, line)
+                    read.add(name)
+            # getenv with a computed name: only inside the helper itself
+            if re.search(r'\bgetenv\s*\(\s*[^"\s]', code):
+                assert f == 'common.hpp' and 'getenv(name)' in code, (f, line)
+    assert read == documented, (sorted(read - documented), sorted(documented - read))
+    # the Makefile builds the shipped libraries without the lab macro
+    assert 'GN_LAB' not in open(os.path.join(csrc, 'Makefile')).read()
+
+
 def test_no_cpu_fallback_and_no_oracle_in_product():
     from clover_amd import ops
     x = torch.randn(4, 96)

@@ -1,5 +1,4 @@
-"""clv_adamw_step_dev on a 160 M-parameter slab: microseconds and HBM rate (30 B per parameter) for the CLV_ADAM_NT /
-CLV_ADAM_GRID variants."""
+"""clv_adamw_step_dev on a 160 M-parameter slab: microseconds and HBM rate (30 B per parameter)."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -19,4 +18,4 @@ s.record()
 for _ in range(10): run()
 e.record(); torch.cuda.synchronize()
 t = s.elapsed_time(e) / 10 * 1e-3
-print(f'NT={os.environ.get("CLV_ADAM_NT", "0")} GRID={os.environ.get("CLV_ADAM_GRID", "-")}: {t * 1e6:7.1f} us  {30 * n / t / 1e12:5.2f} TB/s')
+print(f'{t * 1e6:7.1f} us  {30 * n / t / 1e12:5.2f} TB/s')

@@ -1,8 +1,9 @@
-// Stand-alone lab for clover_amd/csrc/gemm_nt.hip (no torch): includes the kernel source with -DGN_TRACE, so every launch
+// Stand-alone lab for clover_amd/csrc/gemm_nt.hip (no torch): includes the kernel source with -DGN_LAB (the forced tile
+// classes of CLV_GEMM_TILE, which the shipped library does not compile) and -DGN_TRACE, so every launch
 // leaves per-workgroup cycle sums of the main loop's phases (wait for the DMA, barrier, DMA issue, LDS reads + MFMAs,
 // epilogue).  Weights rotate over copies that together exceed the Infinity Cache ("cold W", as in the step); the
 // activation stays hot.  Build (cross-compiles without a GPU):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -DGN_TRACE -I clover_amd/csrc -I include \
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -DGN_LAB -DGN_TRACE -I clover_amd/csrc -I include \
 //         tools/probes/gemm_lab.cpp -o tools/probes/bin/gemm_lab
 // Run:  CLV_GEMM_TILE=... CLV_GEMM_ROT=... tools/probes/bin/gemm_lab [epilogue]
 #include "gemm_nt.hip"

@@ -1,6 +1,9 @@
 """clv_gemm_nt variants vs the tuned library GEMM on every Linear shape of the step that runs on it: K rotation
 (CLV_GEMM_ROT), K slices (CLV_GEMM_SPLITK), tile classes (CLV_GEMM_TILE).  Device-side time per launch (us): n launches
 captured in one hipGraph, replayed.   python tools/probes/gemm_sweep.py [quick] [coldw]
+The forced tile classes (CLV_GEMM_TILE) exist only in a -DGN_LAB library: build it with
+    bash tools/probes/build_wg_variants.sh gemm_nt lab "-DGN_LAB"
+and run this probe with CLOVER_HALF=bf16 CLOVER_LIB_PATH=tools/probes/bin/libclover_lab.so (the shipped library ignores the variable).
 coldw: every launch of the graph reads a DIFFERENT copy of the weight (copies total > 600 MB: more than the 256 MB
 Infinity Cache), as in the step, where a layer's weight was last touched a step ago; the activation stays hot (its
 producer has just written it)."""
@@ -47,7 +50,6 @@ VARIANTS = [('base', dict(CLV_GEMM_ROT='0', CLV_GEMM_SPLITK='1')),
             ('rot+s8', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='8')),
             ('rot 64x128', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='1', CLV_GEMM_TILE='64x128w4')),
             ('rot 128w8r2', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='1', CLV_GEMM_TILE='128x128w8r2')),
-            ('rot 128w4', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='1', CLV_GEMM_TILE='128x128w4')),
             ('rot 256x128', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='1', CLV_GEMM_TILE='256x128')),
             ('rot 128w8r4', dict(CLV_GEMM_ROT='1', CLV_GEMM_SPLITK='1', CLV_GEMM_TILE='128x128w8'))]
 KEYS = ('CLV_GEMM_ROT', 'CLV_GEMM_SPLITK', 'CLV_GEMM_TILE')

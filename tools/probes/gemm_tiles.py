@@ -1,6 +1,9 @@
 """clv_gemm_nt tile classes vs the tuned library GEMM on the long-contraction / few-tile Linear shapes of the step
 (Swin stage 3, fusion encoder, text tower, long-K layers of stages 1-2).  Device-side time per launch by HIP events over
-back-to-back launches (us).   python tools/probes/gemm_tiles.py"""
+back-to-back launches (us).  The forced tile classes (CLV_GEMM_TILE) exist only in a -DGN_LAB library:
+    bash tools/probes/build_wg_variants.sh gemm_nt lab "-DGN_LAB"
+    CLOVER_HALF=bf16 CLOVER_LIB_PATH=tools/probes/bin/libclover_lab.so python tools/probes/gemm_tiles.py
+(the shipped library ignores the variable: every column then shows the planner's class)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -32,7 +35,7 @@ SH = [(50176, 192, 768, 'fc2 s1'), (12544, 384, 1536, 'fc2 s2'), (12544, 384, 76
       (3136, 2304, 768, 'qkv s3'), (3136, 768, 768, 'proj s3'), (3136, 3072, 768, 'fc1 s3'), (3136, 768, 3072, 'fc2 s3'),
       (3648, 2304, 768, 'qkv fu'), (3648, 768, 768, 'out fu'), (3648, 3072, 768, 'fc1 fu'), (3648, 768, 3072, 'fc2 fu'),
       (512, 2304, 768, 'qkv bert'), (512, 768, 768, 'out bert'), (512, 3072, 768, 'fc1 bert'), (512, 768, 3072, 'fc2 bert')]
-TILES = [None, '128x128w4', '128x128w8r2']
+TILES = [None, '64x128w4', '128x128w8r2']
 if os.environ.get('SHAPES') == 'shortk':      # the short-contraction token-parallel layers of stages 1-2
     SH = SHORTK
 for (M, N, K, name) in SH:
@@ -47,9 +50,9 @@ for (M, N, K, name) in SH:
         try:
             y = ops.gemm_nt(x, w, b, epilogue=1)
             err = ((y.float() - ref).abs().max() / ref.abs().max()).item()
-            res.append((t or '128x128', timeit(lambda: ops.gemm_nt(x, w, b, epilogue=1)), err))
+            res.append((t or 'planner', timeit(lambda: ops.gemm_nt(x, w, b, epilogue=1)), err))
         except RuntimeError as e:
-            res.append((t or '128x128', float('nan'), -1))
+            res.append((t or 'planner', float('nan'), -1))
     os.environ.pop('CLV_GEMM_TILE', None)
     fl = 2 * M * N * K
     print(f'{name:9s} M={M:6d} N={N:5d} K={K:5d}: lib {t_lib:6.1f} ({fl / t_lib / 1e6:5.0f} TF) | ' +

@@ -16,4 +16,4 @@ s.record()
 for _ in range(20): ops.flush_wgrads(pend)
 e.record(); torch.cuda.synchronize()
 t = s.elapsed_time(e) / 20 * 1e-3
-print(f'BIG={os.environ.get("CLV_WGRAD_BIG", "1")} {n} x ({M},{N},{K}): {t * 1e6:7.1f} us  {n * 2 * M * N * K / t / 1e12:6.1f} TFLOP/s  {n * 2 * M * (N + K) / t / 1e12:5.2f} TB/s', flush=True)
+print(f'{n} x ({M},{N},{K}): {t * 1e6:7.1f} us  {n * 2 * M * N * K / t / 1e12:6.1f} TFLOP/s  {n * 2 * M * (N + K) / t / 1e12:5.2f} TB/s', flush=True)

@@ -1,5 +1,6 @@
 """The video tower's deferred weight gradients as the grouped launches the step makes (clv_linear_wgrad_batch), timed
-with events; CLV_WGRAD_GROUP_TARGET overrides the per-problem workgroup target for sweeps."""
+with events (ONLY=s0..s3: one stage's problems; to sweep a tuning constant of gemm_wgrad.hip, build variant libraries with
+build_wg_variants.sh and run this under CLOVER_LIB_PATH)."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
