@@ -83,6 +83,9 @@ class ClvLnReduceEntry(C.Structure):
                 ('pad', _i32)]
 
 
+LN_REDUCE_MAX = 64
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),

@@ -6,6 +6,7 @@ are what the registered nn.Modules call.  No CPU path exists: a non-HIP tensor r
 import ctypes as C
 
 import os
+from typing import Any, NamedTuple, Optional
 
 import torch
 
@@ -277,11 +278,11 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
     M, N = dy2.shape
     K = x2.shape[1]
     sink = dw_out is not None
-    ow = first_touch(dw_out)
+    first = first_touch(dw_out)
     # fused gradient norm (engine, one rank): this sink's sum of squares is delivered by whoever WRITES it — the grouped /
-    # fold kernels through their norm slots (flag bit 2), every other path by an explicit pass over the sink right here
+    # fold kernels through their norm slots (DELIVER_SUMSQ), every other path by an explicit pass over the sink right here
     ssq = getattr(dw_out, '_clv_ssq', None) if sink else None
-    if ssq is not None and not ow:
+    if ssq is not None and not first:
         # a SECOND gradient for a sink whose sum of squares rode on its first one (a caller running two backward passes
         # between optimizer steps): the fused sums no longer describe the slab — the engine recomputes the whole norm
         ssq[2].dirty = True
@@ -291,13 +292,14 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
         xstats = None
     if _wgrad_custom(M, N, K):
         L = _lib.lib()
-        if WGRAD_DEFER is not None and sink and xstats is None:
+        if SEGMENT is not None and SEGMENT.wgrads is not None and sink and xstats is None:
             # nothing reads a weight gradient before the optimizer: this launch joins the grouped one that closes the
             # backward segment (dy2 / x2 stay alive in the list until then)
-            WGRAD_DEFER.append((dy2, x2, dw_out, db_out if want_bias else None, M, N, K,
-                                (1 if ow else 0) | (4 if ssq is not None else 0), torch.cuda.current_stream().cuda_stream))
+            SEGMENT.wgrads.append(WgradItem(dy2, x2, dw_out, db_out if want_bias else None, M, N, K,
+                                            (STORE_DW if first else 0) | (DELIVER_SUMSQ if ssq is not None else 0),
+                                            torch.cuda.current_stream().cuda_stream))
             return None, None
-        if ow:
+        if first:
             dw_out.zero_()                     # the stand-alone launches only accumulate
         dw = dw_out if sink else torch.zeros(N, K, device=dy2.device, dtype=torch.float32)
         db = (db_out if sink else torch.zeros(N, device=dy2.device, dtype=torch.float32)) if want_bias else None
@@ -307,10 +309,10 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
         slices = L.clv_linear_wgrad_splits(M, N, K)
         needs_fold = slices > 1 or xstats is not None       # one slice without standardisation: atomics straight into dW
         if PROF is None:
-            if FOLD_DEFER is not None and sink and needs_fold:
-                # partial kernel now, its fold in the ONE batched launch that closes this backward segment
+            if SEGMENT is not None and sink and needs_fold:
+                # partial kernel now, its fold in the segment's ONE batched launch (a stale dw was zeroed above: += is =)
                 check(L.clv_linear_wgrad(*args, 1, _stream()), 'clv_linear_wgrad')
-                FOLD_DEFER.append((work, dw, db, N, K, slices, 4 if ssq is not None else 0))   # (dw was zeroed above: += is =)
+                SEGMENT.folds.append(FoldItem(work, dw, db, N, K, slices, DELIVER_SUMSQ if ssq is not None else 0))
             else:
                 check(L.clv_linear_wgrad(*args, 0, _stream()), 'clv_linear_wgrad')
                 if ssq is not None:
@@ -334,7 +336,7 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
             db.add_(dy2.sum(0, dtype=torch.float32))
     _library_gemm('linear_wgrad', (M, N, K))
     if sink:
-        if ow:
+        if first:
             torch.mm(dy2.t(), x2, out_dtype=torch.float32, out=dw_out)
         else:
             torch.addmm(dw_out, dy2.t(), x2, out_dtype=torch.float32, out=dw_out)
@@ -344,42 +346,74 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
     return torch.mm(dy2.t(), x2, out_dtype=torch.float32), db
 
 
-FOLD_DEFER = None           # list while a backward segment defers its weight-gradient folds (defer_folds())
-LN_DEFER = None             # ... and the reductions of its LayerNorm-backward partials
-WGRAD_DEFER = None          # ... and whole weight-gradient launches (grouped into one grid)
-POST_DEFER = None           # ... and what consumes a deferred weight gradient (the LayerNorm un-fold), run after the folds
-DBIAS_DEFER = None          # ... and the table-gradient gathers of the window-attention blocks (one launch for all of them)
+# Flag bits of a deferred item: the `overwrite` fields of ClvWgradEntry / ClvFoldEntry (include/clover_hip.h)
+STORE_DW = 1                # dW is stored, not added: a first-touch sink, or an uninitialised temporary
+STORE_DB = 2                # ... and db too (folds only)
+DELIVER_SUMSQ = 4           # whoever writes dW adds its sum of squares to the sink's norm slots (fused gradient norm)
 
 
-class defer_folds:
-    """Context: the weight-gradient launches inside write their fp32 partials only; ONE clv_wgrad_fold_batch launch on
-    exit adds them into the gradient slabs (a backward pass otherwise pays ~44 launch-bound 5-7 us fold kernels).
-    Only for gradients nobody reads before the context closes (the engine wraps whole backward segments)."""
+class WgradItem(NamedTuple):        # a deferred dw += dy^T x, db += colsum(dy); dy and x stay alive in it until the launch
+    dy: Any
+    x: Any
+    dw: Any
+    db: Any
+    M: int
+    N: int
+    K: int
+    flags: int = 0
+    stream: Optional[int] = None    # raw handle of the stream it was queued from; None: waits for the segment's end
+
+
+class FoldItem(NamedTuple):         # a deferred fold of `splits` fp32 partial slabs [N*K dW | N db] into dw / db
+    partial: Any
+    dw: Any
+    db: Any
+    N: int
+    K: int
+    splits: int
+    flags: int = 0
+
+
+# a deferred reduction of a LayerNorm backward's per-block partials [2][nblk][C] into dgamma / dbeta, and a deferred
+# relative-position-table gather: the planned ClvDbiasGather and the tensors it points into
+LnReduceItem = NamedTuple('LnReduceItem', [('partial', Any), ('dgamma', Any), ('dbeta', Any), ('nblk', int), ('C', int)])
+DbiasItem = NamedTuple('DbiasItem', [('entry', Any), ('partial', Any), ('dtable', Any), ('index', Any)])
+
+
+class Segment:
+    """Context (ops.defer_folds()): what a backward segment postpones to its end — the engine wraps whole backward segments,
+    nobody reads these gradients before the optimizer.  Weight-gradient launches (`wgrads`; None with CLOVER_GROUP_WGRAD=0:
+    they go out at once), the `folds` of their partials (ONE launch instead of ~44 launch-bound 5-7 us fold kernels per pass),
+    the LayerNorm un-folds that consume them (`post`, callables), LayerNorm reductions (`ln_reduces`), table gathers (`dbias`)."""
+
+    def __init__(self):
+        self.wgrads = [] if os.environ.get('CLOVER_GROUP_WGRAD', '1') == '1' else None
+        self.folds, self.post, self.ln_reduces, self.dbias = [], [], [], []
 
     def __enter__(self):
-        global FOLD_DEFER, LN_DEFER, WGRAD_DEFER, POST_DEFER, DBIAS_DEFER
-        self.prev_db, DBIAS_DEFER = DBIAS_DEFER, []
-        self.prev, FOLD_DEFER = FOLD_DEFER, []
-        self.prev_ln, LN_DEFER = LN_DEFER, []
-        self.prev_wg, WGRAD_DEFER = WGRAD_DEFER, ([] if os.environ.get('CLOVER_GROUP_WGRAD', '1') == '1' else None)
-        self.prev_post, POST_DEFER = POST_DEFER, []
+        global SEGMENT
+        self.prev, SEGMENT = SEGMENT, self
         return self
 
     def __exit__(self, *exc):
-        global FOLD_DEFER, LN_DEFER, WGRAD_DEFER, POST_DEFER, DBIAS_DEFER
-        pending_db, DBIAS_DEFER = DBIAS_DEFER, self.prev_db
-        pending, FOLD_DEFER = FOLD_DEFER, self.prev
-        pending_ln, LN_DEFER = LN_DEFER, self.prev_ln
-        pending_wg, WGRAD_DEFER = WGRAD_DEFER, self.prev_wg
-        pending_post, POST_DEFER = POST_DEFER, self.prev_post
+        global SEGMENT
+        SEGMENT = self.prev
         if exc[0] is None:                 # (a backward segment that raised launches nothing that it deferred)
-            pending = pending + flush_wgrads(pending_wg or [])
-            flush_folds(pending)
-            for fn in pending_post:
+            flush_folds(self.folds + flush_wgrads(self.wgrads or []))    # (the folds those produced included)
+            for fn in self.post:
                 fn()
-            flush_ln_reduces(pending_ln)
-            flush_dbias_gathers(pending_db)
-        return False
+            flush_ln_reduces(self.ln_reduces)
+            flush_dbias_gathers(self.dbias)
+
+    def take_stream_wgrads(self, stream):
+        """Remove and return the weight gradients queued from `stream` (a raw handle); the others keep their order."""
+        mine = [it for it in self.wgrads if it.stream == stream]
+        self.wgrads[:] = [it for it in self.wgrads if it.stream != stream]
+        return mine
+
+
+defer_folds = Segment       # the name its users know: `with ops.defer_folds(): <backward segment>`
+SEGMENT = None              # the open Segment; one plain global: autograd runs one device's backward on one thread
 
 
 def flush_stream_wgrads():
@@ -390,17 +424,8 @@ def flush_stream_wgrads():
     (The same for the heads' / fusion encoder's gradients on an auxiliary stream was measured and dropped: same-box
     11.09 / 11.16 -> 11.28 / 11.33 ms — MFMA-heavy grouped launches beside the video chain take the CUs and the HBM that
     chain is bound by, as the early video launches of round 4 did.)"""
-    global WGRAD_DEFER
-    if WGRAD_DEFER is None or not WGRAD_DEFER:
-        return
-    cur = torch.cuda.current_stream().cuda_stream
-    mine = [it for it in WGRAD_DEFER if len(it) > 8 and it[8] == cur]
-    if not mine:
-        return
-    WGRAD_DEFER[:] = [it for it in WGRAD_DEFER if not (len(it) > 8 and it[8] == cur)]
-    folds = flush_wgrads(mine)
-    if folds:
-        flush_folds(folds)
+    if SEGMENT is not None and SEGMENT.wgrads:
+        flush_folds(flush_wgrads(SEGMENT.take_stream_wgrads(torch.cuda.current_stream().cuda_stream)))
 
 
 class _FlushPoint(torch.autograd.Function):
@@ -421,50 +446,51 @@ def flush_point(x):
     return x
 
 
-def wgrad_chunks(pending):
-    """Split the deferred weight gradients (dy, x, dW, db, M, N, K, ...) into launches of <= WGRAD_GROUP_MAX problems.
-    In-place problems (few rows / very large outputs: clv_linear_wgrad_in_place) add into dW without atomics, so two of
-    them with the SAME dW (a Linear applied twice in the segment) never share a launch."""
-    L = _lib.lib()
-    chunks, cur, seen = [], [], set()
-    for item in pending:
-        key = item[2].data_ptr() if L.clv_linear_wgrad_in_place(item[4], item[5], item[6]) else None
-        if len(cur) == _lib.WGRAD_GROUP_MAX or (key is not None and key in seen):
-            chunks.append(cur)
-            cur, seen = [], set()
-        cur.append(item)
-        if key is not None:
-            seen.add(key)
-    if cur:
-        chunks.append(cur)
+def _chunks(items, cap, keys):
+    """Split `items`, in order, into launches of <= cap of them in which no conflict key appears twice (keys(item): the
+    addresses its launch adds into WITHOUT atomics, possibly none).  Greedy: a launch closes when it is full or the next
+    item's keys meet it; successive launches on a stream are ordered, which keeps those kernels race-free."""
+    chunks, seen = [], set()
+    for item in items:
+        k = keys(item)
+        if not chunks or len(chunks[-1]) == cap or not seen.isdisjoint(k):
+            chunks.append([])
+            seen = set()
+        chunks[-1].append(item)
+        seen.update(k)
     return chunks
 
 
+def wgrad_chunks(pending):
+    """The deferred weight gradients in launches of <= WGRAD_GROUP_MAX problems.  In-place problems (few rows / very large
+    outputs: clv_linear_wgrad_in_place) add into dW without atomics: two with the SAME dW never share a launch."""
+    in_place = _lib.lib().clv_linear_wgrad_in_place
+    return _chunks(pending, _lib.WGRAD_GROUP_MAX, lambda it: (it.dw.data_ptr(),) if in_place(it.M, it.N, it.K) else ())
+
+
 def flush_wgrads(pending):
-    """The deferred weight gradients as grouped launches (clv_linear_wgrad_batch, <= 80 problems each); returns the
-    fold entries of their partials."""
+    """The deferred weight gradients as grouped launches (clv_linear_wgrad_batch); returns the FoldItems of their partials."""
     folds = []
     L = _lib.lib()
     for chunk in wgrad_chunks(pending):
         arr = (_lib.ClvWgradEntry * len(chunk))()
-        for e, (dy2, x2, dw, db, M, N, K, *_) in zip(arr, chunk):
-            e.dy, e.x, e.M, e.N, e.K = dy2.data_ptr(), x2.data_ptr(), M, N, K
-            e.ldy, e.ldx, e.want_bias = dy2.stride(0), x2.stride(0), int(db is not None)
+        for e, it in zip(arr, chunk):
+            e.dy, e.x, e.M, e.N, e.K = it.dy.data_ptr(), it.x.data_ptr(), it.M, it.N, it.K
+            e.ldy, e.ldx, e.want_bias = it.dy.stride(0), it.x.stride(0), int(it.db is not None)
         check(L.clv_linear_wgrad_batch_plan(arr, len(chunk)), 'clv_linear_wgrad_batch_plan')
-        work = torch.empty(max(1, sum(e.work_floats for e in arr)), device=chunk[0][0].device, dtype=torch.float32)
+        work = torch.empty(max(1, sum(e.work_floats for e in arr)), device=chunk[0].dy.device, dtype=torch.float32)
         off = 0
-        slots = None                                 # norm slots of the sinks whose sum of squares the kernels deliver (bit 2)
-        for e, (dy2, x2, dw, db, M, N, K, *ow) in zip(arr, chunk):
-            flags = int(ow[0]) if ow else 0          # bit 0: dW is stored (first touch / temporary), bit 1: db too
-            if flags & 4:
-                slots = dw._clv_ssq[1]
+        slots = None                                 # norm slots of the sinks whose sum of squares the kernels deliver
+        for e, it in zip(arr, chunk):
+            if it.flags & DELIVER_SUMSQ:
+                slots = it.dw._clv_ssq[1]
             if e.work_floats == 0:                   # few-row problem: accumulated in place, nothing to fold
-                e.dw, e.db = dw.data_ptr(), (db.data_ptr() if db is not None else None)
-                e.overwrite = flags & 5
+                e.dw, e.db = it.dw.data_ptr(), (it.db.data_ptr() if it.db is not None else None)
+                e.overwrite = it.flags & (STORE_DW | DELIVER_SUMSQ)
                 continue
             w = work[off:off + e.work_floats]
             e.work = w.data_ptr()
-            folds.append((w, dw, db, N, K, e.splits, flags))
+            folds.append(FoldItem(w, it.dw, it.db, it.N, it.K, e.splits, it.flags))
             off += e.work_floats
         if PROF is None:
             check(L.clv_linear_wgrad_batch_ss(arr, len(chunk), _ptr(slots), _stream()), 'clv_linear_wgrad_batch')
@@ -480,61 +506,39 @@ def flush_wgrads(pending):
 
 
 def fold_chunks(pending):
-    """Split the deferred folds (partial, dW, db, ...) into launches of <= FOLD_MAX entries in which no dW (and no db)
-    appears twice: fold_batch_kernel adds with a plain load / add / store, every entry from its own blocks, so two
-    entries with one target in ONE launch would race (a Linear applied twice inside a backward segment on the partial
-    path — ADVICE r2).  Successive launches on the stream are ordered."""
-    chunks, cur, seen = [], [], set()
-    for item in pending:
-        keys = {item[1].data_ptr()} | ({item[2].data_ptr()} if item[2] is not None else set())
-        if len(cur) == _lib.FOLD_MAX or (keys & seen):
-            chunks.append(cur)
-            cur, seen = [], set()
-        cur.append(item)
-        seen |= keys
-    if cur:
-        chunks.append(cur)
-    return chunks
+    """The deferred folds in launches of <= FOLD_MAX entries in which no dW (and no db) appears twice: fold_batch_kernel
+    adds with a plain load / add / store, every entry from its own blocks, so two entries with one target in ONE launch
+    would race (a Linear applied twice inside a backward segment on the partial path — ADVICE r2)."""
+    return _chunks(pending, _lib.FOLD_MAX,
+                   lambda it: (it.dw.data_ptr(),) if it.db is None else (it.dw.data_ptr(), it.db.data_ptr()))
 
 
 def flush_folds(pending):
     for chunk in fold_chunks(pending):
         arr = (_lib.ClvFoldEntry * len(chunk))()
         slots = None
-        for e, (work, dw, db, N, K, slices, *ow) in zip(arr, chunk):
-            e.partial, e.dw, e.db = work.data_ptr(), dw.data_ptr(), (db.data_ptr() if db is not None else None)
-            e.nk, e.e2, e.splits = N * K, N * K + N, slices
-            e.overwrite = int(ow[0]) if ow else 0
-            if e.overwrite & 4:                      # the fold delivers this sink's sum of squares (fused gradient norm)
-                slots = dw._clv_ssq[1]
+        for e, it in zip(arr, chunk):
+            e.partial, e.dw, e.db = it.partial.data_ptr(), it.dw.data_ptr(), (it.db.data_ptr() if it.db is not None else None)
+            e.nk, e.e2, e.splits, e.overwrite = it.N * it.K, it.N * it.K + it.N, it.splits, it.flags
+            if it.flags & DELIVER_SUMSQ:             # the fold delivers this sink's sum of squares (fused gradient norm)
+                slots = it.dw._clv_ssq[1]
         check(_lib.lib().clv_wgrad_fold_batch_ss(arr, len(chunk), _ptr(slots), _stream()), 'clv_wgrad_fold_batch')
 
 
 def flush_dbias_gathers(pending):
-    """The deferred table-gradient gathers (entry, work, d table, index) as launches of <= DBIAS_GATHER_MAX blocks; two
-    gathers into the SAME table (a module applied twice in the segment) never share a launch — each adds without atomics."""
-    chunk, seen = [], set()
-
-    def go():
-        if chunk:
-            arr = (_lib.ClvDbiasGather * len(chunk))(*[c[0] for c in chunk])
-            check(_lib.lib().clv_attn_dbias_gather_batch(arr, len(chunk), _stream()), 'clv_attn_dbias_gather_batch')
-    for item in pending:
-        key = item[2].data_ptr()
-        if len(chunk) == _lib.DBIAS_GATHER_MAX or key in seen:
-            go()
-            chunk, seen = [], set()
-        chunk.append(item)
-        seen.add(key)
-    go()
+    """The deferred table-gradient gathers (DbiasItem) as launches of <= DBIAS_GATHER_MAX blocks; two gathers into the
+    SAME table (a module applied twice in the segment) never share a launch — each adds without atomics."""
+    for chunk in _chunks(pending, _lib.DBIAS_GATHER_MAX, lambda it: (it.dtable.data_ptr(),)):
+        arr = (_lib.ClvDbiasGather * len(chunk))(*[it.entry for it in chunk])
+        check(_lib.lib().clv_attn_dbias_gather_batch(arr, len(chunk), _stream()), 'clv_attn_dbias_gather_batch')
 
 
 def flush_ln_reduces(pending):
-    for i in range(0, len(pending), 64):
-        chunk = pending[i:i + 64]
+    for chunk in _chunks(pending, _lib.LN_REDUCE_MAX, lambda it: ()):      # (the kernel adds with atomics: no key)
         arr = (_lib.ClvLnReduceEntry * len(chunk))()
-        for e, (partial, dg, db, nblk, C_) in zip(arr, chunk):
-            e.partial, e.dgamma, e.dbeta, e.nblk, e.C = partial.data_ptr(), dg.data_ptr(), db.data_ptr(), nblk, C_
+        for e, it in zip(arr, chunk):
+            e.partial, e.dgamma, e.dbeta = it.partial.data_ptr(), it.dgamma.data_ptr(), it.dbeta.data_ptr()
+            e.nblk, e.C = it.nblk, it.C
         check(_lib.lib().clv_ln_reduce_batch(arr, len(chunk), _stream()), 'clv_ln_reduce_batch')
 
 
@@ -890,7 +894,7 @@ def _wgrad_folded(dy2, xhat, xs, mean, rstd, weight, bias, gamma, beta):
     defer_folds() with engine-managed parameters both are deferred: the GEMM joins the grouped launch (into a zeroed
     temporary), the un-fold kernel runs after the folds."""
     ps = (weight, bias, gamma, beta)
-    if (WGRAD_DEFER is not None and POST_DEFER is not None and xhat is not None
+    if (SEGMENT is not None and SEGMENT.wgrads is not None and xhat is not None
             and all(getattr(q, '_clv_grad', None) is not None and q._clv_grad.dtype == torch.float32
                     for q in ps if q is not None)):
         (M, N), K = dy2.shape, xhat.shape[1]
@@ -899,8 +903,8 @@ def _wgrad_folded(dy2, xhat, xs, mean, rstd, weight, bias, gamma, beta):
             # partial slices + fold: the fold STORES into the temporary (no zero-fill launch); one in-place slice adds
             tmp = (torch.zeros if in_place else torch.empty)(N * K + N, device=dy2.device, dtype=torch.float32)
             dwf, dbf = tmp[:N * K].view(N, K), tmp[N * K:]
-            WGRAD_DEFER.append((dy2, xhat, dwf, dbf, M, N, K, 0 if in_place else 3))
-            POST_DEFER.append(lambda: _unfold_grads(dwf, dbf, weight, bias, gamma, beta))
+            SEGMENT.wgrads.append(WgradItem(dy2, xhat, dwf, dbf, M, N, K, 0 if in_place else STORE_DW | STORE_DB))
+            SEGMENT.post.append(lambda: _unfold_grads(dwf, dbf, weight, bias, gamma, beta))
             return None, None, None, None
     dwf, dbf = linear_wgrad(dy2, xhat, True) if xhat is not None else linear_wgrad(dy2, xs, True, xstats=(mean, rstd))
     return _unfold_grads(dwf, dbf, weight, bias, gamma, beta)
@@ -1451,12 +1455,12 @@ class _LayerNorm(torch.autograd.Function):
             dg = torch.zeros(C_, device=x2.device, dtype=torch.float32)
             db = torch.zeros_like(dg)
         ex = _ln_extra(xs, ctx.rps, ctx.drop_p, seed, dyf2, dres, ctx.x_is_sum)
-        if LN_DEFER is not None and sink and L.clv_layernorm_bwd_needs_reduce(rows, C_):
+        if SEGMENT is not None and sink and L.clv_layernorm_bwd_needs_reduce(rows, C_):
             # leave the per-block partials; ONE batched launch reduces them when the backward segment closes
             if ex is None:
                 ex = _lib.ClvLnExtra(None, 1, 0.0, None, None, None, int(ctx.x_is_sum), 0, 0, 0, 0)
             ex.no_reduce = 1
-            LN_DEFER.append((partial, dg, db, nblk, C_))
+            SEGMENT.ln_reduces.append(LnReduceItem(partial, dg, db, nblk, C_))
         check(L.clv_layernorm_bwd(_ptr(dy2), _ptr(x2), _ptr(r2), _ptr(g), _ptr(mean), _ptr(rstd), _ptr(ds2),
                                   _ptr(dx), _ptr(dg), _ptr(db), _ptr(partial), rows, C_,
                                   int(x2.dtype == torch.float32), C.byref(ex) if ex is not None else None,
@@ -1765,7 +1769,7 @@ class _Attention(torch.autograd.Function):
         args = (C.c_void_p(b), C.c_void_p(b + 2 * Cdim), C.c_void_p(b + 4 * Cdim), _ptr(o), _ptr(doc), _ptr(lse),
                 _ptr(tab), _ptr(rid), _ptr(kmask), C.c_void_p(d), C.c_void_p(d + 2 * Cdim),
                 C.c_void_p(d + 4 * Cdim), _ptr(dtab), _ptr(dsum), _ptr(work), _ptr(seed))
-        if PROF is None and DBIAS_DEFER is not None and sink is not None:
+        if PROF is None and SEGMENT is not None and sink is not None:
             # nothing reads a table gradient before the optimizer: leave the slices' partial sums in `work` (stage bit 8) and
             # gather every attention block of this backward segment in ONE launch when it closes (flush_dbias_gathers)
             # The partial sums go to a buffer of their own (ClvAttnGeom.work): only that stays alive until the gather — the dS
@@ -1776,7 +1780,7 @@ class _Attention(torch.autograd.Function):
             ent = _lib.ClvDbiasGather()
             check(L.clv_attn_dbias_gather_entry(C.byref(g), _ptr(work), _ptr(dtab), C.byref(ent)), 'clv_attn_dbias_gather_entry')
             g.work = None
-            DBIAS_DEFER.append((ent, part, dtab, g.dbias_index))
+            SEGMENT.dbias.append(DbiasItem(ent, part, dtab, g.dbias_index))
         elif PROF is None:
             check(L.clv_attn_bwd(*args, 0, C.byref(g), _stream()), 'clv_attn_bwd')
         elif tab is not None and L.clv_attn_bwd_one_kernel(C.byref(g)) == 1:
@@ -2150,12 +2154,7 @@ class _MLMDecoder(torch.autograd.Function):
             return dx, None, None
         Wp = rest[0]
         dx = gemm_nt(dyp, Wp.t().contiguous()) if ctx.needs_input_grad[0] else None
-        global WGRAD_DEFER
-        hold, WGRAD_DEFER = WGRAD_DEFER, None            # autograd needs these gradients NOW: never into a deferred group
-        try:
-            dwp, dbp = linear_wgrad(dyp, xb, True)
-        finally:
-            WGRAD_DEFER = hold
+        dwp, dbp = linear_wgrad(dyp, xb, True)           # no sink: never deferred, autograd gets these gradients now
         return dx, dwp[:V].to(weight.dtype), dbp[:V].to(bias.dtype)
 
 

@@ -477,8 +477,8 @@ def test_window_deferred_gather_with_split_slices():
         if deferred:
             with ops().defer_folds():
                 body()
-                pend = ops().DBIAS_DEFER
-                assert [e[0].nsplit for e in pend] == [2, 1]
+                pend = ops().SEGMENT.dbias
+                assert [e.entry.nsplit for e in pend] == [2, 1]
         else:
             body()
         torch.cuda.synchronize()

@@ -507,7 +507,7 @@ def test_grouped_weight_gradient_chunking():
     assert L.clv_linear_wgrad_class(512, 768, 768) == 0                       # few-row problems stay on 128 x 128 tiles
     shared = torch.zeros(768, 768)
     other = [torch.zeros(768, 768) for _ in range(3)]
-    item = lambda dw, M: (None, None, dw, None, M, 768, 768)
+    item = lambda dw, M: ops.WgradItem(None, None, dw, None, M, 768, 768)
     # partial-mode uses of a shared dW may sit together in the GEMM launch (each writes its own partial buffer; their
     # folds are separated below) ...
     assert [len(c) for c in ops.wgrad_chunks([item(shared, 12544), item(shared, 12544), item(other[0], 512)])] == [3]
@@ -518,10 +518,112 @@ def test_grouped_weight_gradient_chunking():
     assert [len(c) for c in ops.wgrad_chunks(many)] == [80, 80, 15]
     # the folds of two partial-mode uses of ONE dW (or db) never share a launch: the fold kernel adds without atomics
     w = [torch.zeros(4) for _ in range(4)]
-    fold = lambda dw, db=None: (torch.zeros(1), dw, db, 2, 2, 4)
+    fold = lambda dw, db=None: ops.FoldItem(torch.zeros(1), dw, db, 2, 2, 4)
     assert [len(c) for c in ops.fold_chunks([fold(shared), fold(other[0]), fold(shared), fold(other[1])])] == [2, 2]
     assert [len(c) for c in ops.fold_chunks([fold(other[0], w[0]), fold(other[1], w[0]), fold(other[2], w[1])])] == [1, 2]
     assert [len(c) for c in ops.fold_chunks([fold(torch.zeros(2, 2)) for _ in range(130)])] == [64, 64, 2]
+
+
+def test_chunker_properties():
+    """ops._chunks, the one rule that keeps the no-atomics batched kernels race-free, on seeded random item lists: the chunks
+    concatenate to the input, none exceeds the cap, no conflict key appears twice in one, and the split is greedy (a chunk
+    starts only where its first item would have broken the cap or met a key of the chunk before it)."""
+    import random
+    from clover_amd import ops
+    rng = random.Random(20)
+    for trial in range(400):
+        cap = 1 + trial % 5
+        items = [(i, frozenset(rng.sample('abcd', rng.choice((0, 0, 1, 1, 2))))) for i in range(rng.randrange(0, 24))]
+        chunks = ops._chunks(items, cap, lambda it: it[1])
+        assert [it for c in chunks for it in c] == items and all(chunks)
+        for j, c in enumerate(chunks):
+            assert len(c) <= cap
+            keys = [k for it in c for k in it[1]]
+            assert len(keys) == len(set(keys)), (trial, c)
+            if j:
+                before = chunks[j - 1]
+                assert len(before) == cap or c[0][1] & {k for it in before for k in it[1]}, (trial, before, c[0])
+    assert ops._chunks([], 3, lambda it: ()) == []
+
+
+def test_segment_lifecycle(monkeypatch):
+    """ops.defer_folds(): one open segment in ops.SEGMENT; a nested one flushes its own items at ITS exit and restores the
+    outer one; a body that raises flushes nothing and restores the previous state; a clean exit runs grouped weight
+    gradients, all folds (the ones those produced included), the post callables, LayerNorm reductions, table gathers — in
+    that order; CLOVER_GROUP_WGRAD=0 leaves `wgrads` None and the other lists in place."""
+    from clover_amd import ops
+    log = []
+    monkeypatch.setattr(ops, 'flush_wgrads', lambda p: (log.append(('wgrads', list(p))), ['made:%s' % i for i in p])[1])
+    for name in ('flush_folds', 'flush_ln_reduces', 'flush_dbias_gathers'):
+        monkeypatch.setattr(ops, name, lambda p, name=name: log.append((name[6:], list(p))))
+    monkeypatch.delenv('CLOVER_GROUP_WGRAD', raising=False)
+
+    def fill(tag):
+        seg = ops.SEGMENT
+        seg.dbias.append(tag + 'd'), seg.ln_reduces.append(tag + 'l'), seg.post.append(lambda: log.append(('post', tag)))
+        seg.folds.append(tag + 'f'), seg.wgrads.append(tag + 'w')
+
+    def flushed(tag):
+        return [('wgrads', [tag + 'w']), ('folds', [tag + 'f', 'made:' + tag + 'w']), ('post', tag),
+                ('ln_reduces', [tag + 'l']), ('dbias_gathers', [tag + 'd'])]
+    assert ops.SEGMENT is None
+    with ops.defer_folds():
+        outer = ops.SEGMENT
+        assert isinstance(outer, ops.Segment)
+        fill('o')
+        with ops.defer_folds():
+            assert ops.SEGMENT is not outer and ops.SEGMENT.folds == []
+            fill('i')
+        assert ops.SEGMENT is outer and log == flushed('i')
+        del log[:]
+        with pytest.raises(KeyError):
+            with ops.defer_folds():
+                fill('x')
+                raise KeyError('body')
+        assert ops.SEGMENT is outer and log == []
+    assert ops.SEGMENT is None and log == flushed('o')
+    del log[:]
+    with pytest.raises(KeyError):
+        with ops.defer_folds():
+            fill('x')
+            raise KeyError('body')
+    assert ops.SEGMENT is None and log == []
+    monkeypatch.setenv('CLOVER_GROUP_WGRAD', '0')
+    with ops.defer_folds():
+        seg = ops.SEGMENT
+        assert seg.wgrads is None and (seg.folds, seg.post, seg.ln_reduces, seg.dbias) == ([], [], [], [])
+    assert [k for k, _ in log] == ['wgrads', 'folds', 'ln_reduces', 'dbias_gathers'] and all(p == [] for _, p in log)
+
+
+def test_segment_take_stream_wgrads(monkeypatch):
+    """Segment.take_stream_wgrads (the by-stream split behind ops.flush_stream_wgrads): the items of one stream leave in
+    their order, the others — those without a stream included — keep theirs; an absent stream takes nothing."""
+    from clover_amd import ops
+    monkeypatch.delenv('CLOVER_GROUP_WGRAD', raising=False)
+    a, b = 0x7f00, 0
+    seg = ops.Segment()
+    items = [ops.WgradItem(None, None, None, None, 8 + i, 8, 8, stream=s) for i, s in enumerate((a, b, None, a, b))]
+    seg.wgrads.extend(items)
+    held = seg.wgrads
+    assert seg.take_stream_wgrads(0x1234) == [] and seg.wgrads == items
+    took = seg.take_stream_wgrads(a)
+    assert len(took) == 2 and took[0] is items[0] and took[1] is items[3]
+    assert seg.wgrads is held and len(held) == 3 and all(x is y for x, y in zip(held, (items[1], items[2], items[4])))
+    assert seg.take_stream_wgrads(a) == [] and len(seg.wgrads) == 3
+    assert items[2].stream is None and items[2].flags == 0 and ops.FoldItem(None, None, None, 2, 2, 4).flags == 0
+
+
+def test_batch_caps_match_the_kernel_sources():
+    """The per-launch caps the host chunks by (_lib.py) are the table sizes of the kernels: the #defines of
+    include/clover_hip.h and WG_GROUP_MAX of gemm_wgrad.hip."""
+    from clover_amd import _lib
+    header = open(os.path.join(ROOT, 'include', 'clover_hip.h')).read()
+    defines = {k: int(v) for k, v in re.findall(r'^#define\s+(CLV_\w+_MAX)\s+(\d+)\s*$', header, re.M)}
+    assert _lib.FOLD_MAX == defines['CLV_FOLD_MAX']
+    assert _lib.LN_REDUCE_MAX == defines['CLV_LN_REDUCE_MAX']
+    assert _lib.DBIAS_GATHER_MAX == defines['CLV_DBIAS_GATHER_MAX']
+    wgrad = open(os.path.join(ROOT, 'clover_amd', 'csrc', 'gemm_wgrad.hip')).read()
+    assert _lib.WGRAD_GROUP_MAX == int(re.search(r'constexpr int WG_GROUP_MAX = (\d+);', wgrad).group(1))
 
 
 def test_fusion_text_outputs_and_token_mean_equal_autograd():

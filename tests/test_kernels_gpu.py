@@ -219,10 +219,10 @@ def test_window_attention_deferred_table_gradient():
         if deferred:
             with ops().defer_folds():
                 body()
-                assert len(ops().DBIAS_DEFER) == 2 * len(inputs)
+                assert len(ops().SEGMENT.dbias) == 2 * len(inputs)
                 # what stays alive until the gather is the partial-sum buffer alone, not the block's dS scratch
                 # (clv_attn_bwd_work_bytes: GBs per block at 32 frames — 72 GB over config 5's 24 blocks)
-                held = sum(item[1].numel() for item in ops().DBIAS_DEFER)
+                held = sum(item.partial.numel() for item in ops().SEGMENT.dbias)
                 assert held < 40 * 2 ** 20, held
         else:
             body()
@@ -727,7 +727,7 @@ def test_grouped_weight_gradients_and_batched_fold():
             r = ops().linear_wgrad(dy.to(DEV), x.to(DEV), db is not None, dw, db)
             assert r == (None, None)
             sinks.append((dw, db))
-        assert len(ops().WGRAD_DEFER) == len(shapes)        # every one deferred, none on the library (ops._wgrad_custom)
+        assert len(ops().SEGMENT.wgrads) == len(shapes)        # every one deferred, none on the library (ops._wgrad_custom)
     assert not [k for k in ops().LIBRARY_GEMM_CALLS if k[0] == 'linear_wgrad']
     for (dy, x, dw0, db0), (dw, db) in zip(probs, sinks):
         ref = dw0 + dy.float().t() @ x.float()
@@ -771,7 +771,7 @@ def test_grouped_weight_gradients_ragged_shapes_and_strided_operands():
                     dw._clv_ft = st
                 assert ops().linear_wgrad(dy, x, db is not None, dw, db) == (None, None)
                 sinks.append((dw, db))
-            assert len(ops().WGRAD_DEFER) == len(shapes)
+            assert len(ops().SEGMENT.wgrads) == len(shapes)
     for (dy, x, dw0, db0, first), (dw, db), shp in zip(probs, sinks, shapes):
         ref = dy.double().t() @ x.double()
         if not first:
@@ -794,8 +794,46 @@ def test_grouped_weight_gradients_shared_sink():
             assert ops().linear_wgrad(dy.to(DEV), x.to(DEV), True, dw, db) == (None, None)
             ref_w += dy.float().t() @ x.float()
             ref_b += dy.float().sum(0)
-        assert len(ops().WGRAD_DEFER) == 4
+        assert len(ops().SEGMENT.wgrads) == 4
     assert rel(dw, ref_w) < 2e-5 and rel(db, ref_b) < 2e-5
+
+
+def test_flush_stream_wgrads_on_a_side_stream():
+    """ops.flush_stream_wgrads(): of the weight gradients a segment holds, the ones queued from the CURRENT stream (and the
+    folds of their partials) go out on it at once, the others stay pending until the segment closes — one in-place and one
+    partial + fold problem from each of two streams, every sink against its fp64 reference (dw0 + dy^T x, db0 + colsum dy)."""
+    L = _clv_lib.lib()
+    shapes = [(77, 136, 72), (2000, 136, 104)]
+    assert [L.clv_linear_wgrad_in_place(*s) for s in shapes] == [1, 0]
+    probs = []
+    for i, (M, N, K) in enumerate(shapes * 2):               # problems 0, 1: main stream; 2, 3: side stream
+        dy, x = rnd(M, N, seed=1500 + i).to(BF), rnd(M, K, seed=1510 + i).to(BF)
+        dw0, db0 = rnd(N, K, seed=1520 + i), rnd(N, seed=1530 + i)
+        probs.append((dy, x, dw0, db0, dy.to(DEV), x.to(DEV), dw0.clone().to(DEV), db0.clone().to(DEV)))
+
+    def check(group):
+        for dy, x, dw0, db0, _, _, dw, db in group:
+            ref_w, ref_b = dw0.double() + dy.double().t() @ x.double(), db0.double() + dy.double().sum(0)
+            err_w = ((dw.double().cpu() - ref_w).abs().max() / ref_w.abs().max()).item()
+            err_b = ((db.double().cpu() - ref_b).abs().max() / ref_b.abs().max()).item()
+            assert err_w < 2e-5 and err_b < 2e-5, (tuple(dy.shape), err_w, err_b)
+    side = torch.cuda.Stream()
+    with ops().defer_folds():
+        for _, _, _, _, dy, x, dw, db in probs[:2]:
+            assert ops().linear_wgrad(dy, x, True, dw, db) == (None, None)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _, _, _, _, dy, x, dw, db in probs[2:]:
+                assert ops().linear_wgrad(dy, x, True, dw, db) == (None, None)
+            assert len(ops().SEGMENT.wgrads) == 4
+            ops().flush_stream_wgrads()
+        pend = ops().SEGMENT.wgrads
+        assert len(pend) == 2 and all(it.dw is p[6] and it.stream == torch.cuda.current_stream().cuda_stream
+                                      for it, p in zip(pend, probs[:2]))
+        side.synchronize()
+        check(probs[2:])
+    torch.cuda.synchronize()
+    check(probs[:2])
 
 
 @pytest.mark.parametrize('group', ['1', '0'])           # grouped launch / per-layer partial kernels with deferred folds

@@ -8,7 +8,7 @@ M, N, K, n = [int(a) for a in sys.argv[1:5]]
 pend = []
 for i in range(n):
     dy = torch.randn(M, N, device='cuda').to(torch.bfloat16); x = torch.randn(M, K, device='cuda').to(torch.bfloat16)
-    pend.append((dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
+    pend.append(ops.WgradItem(dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
 for _ in range(3): ops.flush_wgrads(pend)
 torch.cuda.synchronize()
 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -25,7 +25,7 @@ if order == 'bigfirst':
 pend = []
 for (M, N, K) in P:
     dy = torch.randn(M, N, device='cuda').to(ops.BF16); x = torch.randn(M, K, device='cuda').to(ops.BF16)
-    pend.append((dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
+    pend.append(ops.WgradItem(dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
 def run():
     return ops.flush_wgrads(pend)
 for _ in range(3): run()

@@ -27,7 +27,7 @@ def make(P):
     for (M, N, K) in P:
         dy = torch.randn(M, N, device='cuda').to(torch.bfloat16)
         x = torch.randn(M, K, device='cuda').to(torch.bfloat16)
-        pend.append((dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
+        pend.append(ops.WgradItem(dy, x, torch.zeros(N, K, device='cuda'), torch.zeros(N, device='cuda'), M, N, K))
     return pend
 
 
