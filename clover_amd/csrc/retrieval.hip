@@ -1,0 +1,335 @@
+// Text -> video retrieval ranks on the device (gfx950): for every query the 0-based position of its ground-truth
+// gallery row in the stable descending order of its cosine scores, and optionally the first K rows of that order —
+// without ever writing the [Nq, Ng] score matrix.  Restates the host metric of the reference's evaluation stage
+// (mmaction/core/evaluation/accuracy.py:430-462: normalise, dot, argsort, position of the diagonal;
+// mmaction/utils/numpy_norm.py:5-8: all-zero rows stay zero), which needs one number per query and no sort:
+//     rank[i] = #{j : s[i][j] > s[i][g]} + #{j < g : s[i][j] == s[i][g]},   g = gt[i].
+//
+// Three launches (+ one for top-K), all on fp32:
+//   1. retrieval_normalize_kernel: one wave per row, query and gallery rows to unit L2 norm into the work area
+//      (IEEE sqrt and division: a norm of 8 gives exactly 0.125).
+//   2. retrieval_score_kernel<RT_GT>: the score of every query against ITS ground-truth row.  It is the same tile code as
+//      pass 3 with the gallery operand gathered through gt (tile column c holds gallery row gt[m0 + c]; the diagonal of
+//      the tile is what is kept).  v_mfma_f32_16x16x4_f32 is an fmaf chain over k per output element, so a score is a
+//      function of the two rows and of the order of k alone — which both passes share — and gt_score[i] is bit-equal to
+//      the s[i][g] pass 3 computes.  Pass 3 still excludes j == g by index, so even a difference could not count g itself.
+//   3. retrieval_score_kernel<RT_COUNT | RT_TOPK>: a workgroup owns 64 queries and walks a contiguous chunk of the gallery
+//      in 64-row tiles (both operands staged through LDS, 64 x 64 x 16 steps, 4 waves x 32 x 32, as sgemm_tiled_kernel of
+//      parity.hip).  Scores stay in the MFMA accumulators; the epilogue compares them with the row's gt_score and adds up
+//      int32 counts in registers, which meet across the chunks of a long gallery through atomicAdd on int32 (integer
+//      adds commute: deterministic).  With top-K the tile's scores additionally pass through LDS, where one thread per
+//      query inserts them in ascending column order into the query's running list (strict >: ties keep the lower index).
+//   4. retrieval_topk_merge_kernel: one thread per query selects the K best of its chunk lists in the total order
+//      (score descending, index ascending).
+// Padded rows and columns (Nq, Ng not multiples of 64; D not a multiple of 16) are staged as zeros and masked by index
+// in every epilogue: they never count and never enter a list.
+#include "common.hpp"
+#include "../../include/clover_hip.h"
+
+namespace {
+
+constexpr int RT_BM = 64, RT_BN = 64, RT_BK = 16;
+// row stride 18: lanes (lr, lg) of a 32-lane half read word lr * 18 + lg — 16 distinct even banks + their odd
+// neighbours of the 32 ds_read_b32 banks; 17 would put (15, 1) on (0, 0)'s bank
+constexpr int RT_LD = RT_BK + 2;
+constexpr int RT_SLD = RT_BN + 1;          // score tile: thread t walks row t
+constexpr int RT_KMAX = 16, RT_LLD = RT_KMAX + 1;
+constexpr int RT_MAX_CHUNKS = 64;          // bounds the top-K partial table: chunks x Nq x K x 8 bytes
+constexpr int RT_WANT_GROUPS = 512;        // two workgroups per CU before the gallery stops being split
+
+enum { RT_GT = 0, RT_COUNT = 1, RT_TOPK = 2 };
+
+struct RtPlan {
+    int nqb, tiles, tiles_per_chunk, chunks;
+};
+
+inline RtPlan rt_plan(int64_t Nq, int64_t Ng) {
+    RtPlan p;
+    p.nqb = (int)((Nq + RT_BM - 1) / RT_BM);
+    p.tiles = (int)((Ng + RT_BN - 1) / RT_BN);
+    int want = (RT_WANT_GROUPS + p.nqb - 1) / p.nqb;
+    if (want > p.tiles) want = p.tiles;
+    if (want > RT_MAX_CHUNKS) want = RT_MAX_CHUNKS;
+    p.tiles_per_chunk = (p.tiles + want - 1) / want;
+    p.chunks = (p.tiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk;
+    return p;
+}
+
+// one wave per row; rows [0, Nq) are the queries, [Nq, Nq + Ng) the gallery.  out is packed [Nq + Ng][D].
+__global__ void __launch_bounds__(256) retrieval_normalize_kernel(const float* __restrict__ query,
+                                                                  const float* __restrict__ gallery,
+                                                                  float* __restrict__ out, int64_t Nq, int64_t Ng, int D,
+                                                                  int64_t ldq, int64_t ldg) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= Nq + Ng) return;
+    const float* e = row < Nq ? query + row * ldq : gallery + (row - Nq) * ldg;
+    float s = 0.f;
+    for (int d = lane; d < D; d += 64) s += e[d] * e[d];
+    float nrm = sqrtf(wave_sum(s));
+    if (nrm == 0.f) nrm = 1.f;                              // numpy_norm.py:7 — l2[l2 == 0] = 1
+    float* o = out + row * D;
+    for (int d = lane; d < D; d += 64) o[d] = e[d] / nrm;
+}
+
+// qn [Nq][D], gn [Ng][D] packed unit rows.  Grid: (query blocks, gallery chunks); RT_GT: (query blocks, 1).
+template <int MODE>
+__global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __restrict__ qn, const float* __restrict__ gn,
+                                                              const int32_t* __restrict__ gt, int32_t* __restrict__ rank,
+                                                              float* __restrict__ gt_score, float* __restrict__ part_score,
+                                                              int32_t* __restrict__ part_idx, int Nq, int Ng, int D,
+                                                              int tiles_per_chunk, int topk) {
+    __shared__ float As[RT_BM * RT_LD], Bs[RT_BN * RT_LD];
+    __shared__ float Ss[MODE == RT_TOPK ? RT_BM * RT_SLD : 1];
+    __shared__ float Ls[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
+    __shared__ int32_t Li[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lg = lane >> 4, lr = lane & 15;
+    const int m0 = blockIdx.x * RT_BM;
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+    const int srow = tid >> 2, sk = (tid & 3) * 4;           // staging: one float4 of each operand per thread
+
+    // the ground truth of query m: gt[m], or m itself; -1 when the query has none (or it lies outside the gallery)
+    auto truth = [&](int m) -> int {
+        if (m >= Nq) return -1;
+        const int g = gt ? gt[m] : m;
+        return (g >= 0 && g < Ng) ? g : -1;
+    };
+
+    const float* asrc = (m0 + srow < Nq) ? qn + (int64_t)(m0 + srow) * D : nullptr;
+
+    // per-lane view of the accumulators: acc[i][j][r] = s[m0 + wr + i*16 + lg*4 + r][n0 + wc + j*16 + lr]
+    float gs[2][4];
+    int g[2][4], cnt[2][4];
+    if (MODE != RT_GT) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wr + i * 16 + lg * 4 + r;
+                g[i][r] = truth(m);
+                gs[i][r] = g[i][r] >= 0 ? gt_score[m] : 0.f;
+                cnt[i][r] = 0;
+            }
+    }
+    if (MODE == RT_TOPK) {
+        for (int e = tid; e < RT_BM * RT_LLD; e += 256) {
+            Ls[e] = -INFINITY;
+            Li[e] = -1;
+        }
+    }
+
+    const int tile0 = MODE == RT_GT ? 0 : blockIdx.y * tiles_per_chunk;
+    const int tile1 = MODE == RT_GT ? 1 : min(tile0 + tiles_per_chunk, (Ng + RT_BN - 1) / RT_BN);
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int n0 = tile * RT_BN;
+        const float* bsrc;
+        if (MODE == RT_GT) {
+            const int gg = truth(m0 + srow);
+            bsrc = gg >= 0 ? gn + (int64_t)gg * D : nullptr;
+        } else {
+            bsrc = (n0 + srow < Ng) ? gn + (int64_t)(n0 + srow) * D : nullptr;
+        }
+        f32x4_t acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        // D % 4 == 0: a float4 at k is wholly inside the row or wholly outside
+        float4 av = (asrc && sk < D) ? *reinterpret_cast<const float4*>(asrc + sk) : zero4;
+        float4 bv = (bsrc && sk < D) ? *reinterpret_cast<const float4*>(bsrc + sk) : zero4;
+        for (int k0 = 0; k0 < D; k0 += RT_BK) {
+            __syncthreads();                                  // the previous step's fragment reads are done
+            float* as = As + srow * RT_LD + sk;
+            float* bs = Bs + srow * RT_LD + sk;
+            as[0] = av.x; as[1] = av.y; as[2] = av.z; as[3] = av.w;
+            bs[0] = bv.x; bs[1] = bv.y; bs[2] = bv.z; bs[3] = bv.w;
+            __syncthreads();
+            const int kn = k0 + RT_BK + sk;                   // the next step's operands travel under this step's MFMAs
+            av = (asrc && kn < D) ? *reinterpret_cast<const float4*>(asrc + kn) : zero4;
+            bv = (bsrc && kn < D) ? *reinterpret_cast<const float4*>(bsrc + kn) : zero4;
+#pragma unroll
+            for (int k4 = 0; k4 < RT_BK; k4 += 4) {
+                float a[2], b[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    a[i] = As[(wr + i * 16 + lr) * RT_LD + k4 + lg];
+                    b[i] = Bs[(wc + i * 16 + lr) * RT_LD + k4 + lg];
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+
+        if (MODE == RT_GT) {
+            // tile column c holds gallery row gt[m0 + c]: the diagonal is s[m][gt[m]]
+            if (wr == wc) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int m = m0 + wr + i * 16 + lg * 4 + r;
+                        if (lg * 4 + r == lr && m < Nq) {
+                            const bool ok = truth(m) >= 0;
+                            gt_score[m] = ok ? acc[i][i][r] : __builtin_nanf("");
+                            rank[m] = ok ? 0 : -1;
+                        }
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int jg = n0 + wc + j * 16 + lr;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float s = acc[i][j][r];
+                        const bool ahead = s > gs[i][r] || (s == gs[i][r] && jg < g[i][r]);
+                        cnt[i][r] += (jg < Ng && jg != g[i][r] && ahead) ? 1 : 0;
+                        if (MODE == RT_TOPK) Ss[(wr + i * 16 + lg * 4 + r) * RT_SLD + wc + j * 16 + lr] = s;
+                    }
+                }
+            if (MODE == RT_TOPK) {
+                __syncthreads();
+                if (tid < RT_BM && m0 + tid < Nq) {
+                    float* ls = Ls + tid * RT_LLD;
+                    int32_t* li = Li + tid * RT_LLD;
+                    float thr = ls[topk - 1];
+                    const int nc = min(RT_BN, Ng - n0);
+                    for (int c = 0; c < nc; ++c) {
+                        const float s = Ss[tid * RT_SLD + c];
+                        if (s > thr) {                        // a tie with the list's last entry loses: its index is higher
+                            int p = topk - 1;
+                            while (p > 0 && ls[p - 1] < s) {
+                                ls[p] = ls[p - 1];
+                                li[p] = li[p - 1];
+                                --p;
+                            }
+                            ls[p] = s;
+                            li[p] = n0 + c;
+                            thr = ls[topk - 1];
+                        }
+                    }
+                }
+                // the next tile writes Ss only after the syncs of its k loop (D >= 4: at least one step)
+            }
+        }
+    }
+
+    if (MODE != RT_GT) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                int c = cnt[i][r];
+                c += __shfl_xor(c, 1, 64);
+                c += __shfl_xor(c, 2, 64);
+                c += __shfl_xor(c, 4, 64);
+                c += __shfl_xor(c, 8, 64);
+                const int m = m0 + wr + i * 16 + lg * 4 + r;
+                if (lr == 0 && g[i][r] >= 0 && c != 0) atomicAdd(rank + m, c);
+            }
+    }
+    if (MODE == RT_TOPK) {
+        __syncthreads();
+        if (tid < RT_BM && m0 + tid < Nq) {
+            const int64_t base = ((int64_t)blockIdx.y * Nq + (m0 + tid)) * topk;
+            for (int p = 0; p < topk; ++p) {
+                part_score[base + p] = Ls[tid * RT_LLD + p];
+                part_idx[base + p] = Li[tid * RT_LLD + p];
+            }
+        }
+    }
+}
+
+// one thread per query: the K best of chunks x K candidates in the order (score descending, index ascending).  Indices are
+// distinct, so the order is total and "the best candidate after the previous pick" needs no bookkeeping.
+__global__ void __launch_bounds__(256) retrieval_topk_merge_kernel(const float* __restrict__ part_score,
+                                                                   const int32_t* __restrict__ part_idx,
+                                                                   int32_t* __restrict__ topk_idx,
+                                                                   float* __restrict__ topk_score, int Nq, int chunks,
+                                                                   int topk) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nq) return;
+    float ps = INFINITY;
+    int pi = -1;
+    for (int p = 0; p < topk; ++p) {
+        float bs = -INFINITY;
+        int bi = -1;
+        for (int c = 0; c < chunks; ++c) {
+            const int64_t base = ((int64_t)c * Nq + i) * topk;
+            for (int e = 0; e < topk; ++e) {
+                const int ci = part_idx[base + e];
+                if (ci < 0) break;                            // a list is filled from the front
+                const float cs = part_score[base + e];
+                const bool after_prev = cs < ps || (cs == ps && ci > pi);
+                const bool better = bi < 0 || cs > bs || (cs == bs && ci < bi);
+                if (after_prev && better) {
+                    bs = cs;
+                    bi = ci;
+                }
+            }
+        }
+        topk_idx[(int64_t)i * topk + p] = bi;
+        topk_score[(int64_t)i * topk + p] = bi >= 0 ? bs : -INFINITY;
+        if (bi < 0) {                                         // fewer than K gallery rows: the rest is padding
+            for (int q = p + 1; q < topk; ++q) {
+                topk_idx[(int64_t)i * topk + q] = -1;
+                topk_score[(int64_t)i * topk + q] = -INFINITY;
+            }
+            return;
+        }
+        ps = bs;
+        pi = bi;
+    }
+}
+
+inline bool rt_supported(int64_t Nq, int64_t Ng, int32_t D, int32_t topk) {
+    return Nq >= 1 && Ng >= 1 && Nq <= 0x7fffffff - RT_BM && Ng <= 0x7fffffff - RT_BN && D >= 4 && D <= 4096 &&
+           D % 4 == 0 && topk >= 0 && topk <= RT_KMAX;
+}
+
+}  // namespace
+
+extern "C" int64_t clv_retrieval_work_bytes(int64_t Nq, int64_t Ng, int32_t D, int32_t topk) {
+    if (!rt_supported(Nq, Ng, D, topk)) return CLV_ERR_UNSUPPORTED;
+    const RtPlan p = rt_plan(Nq, Ng);
+    return (Nq + Ng) * (int64_t)D * 4 + (int64_t)p.chunks * Nq * topk * 8;
+}
+
+extern "C" int clv_retrieval_rank(const float* query, const float* gallery, const int32_t* gt, int32_t* rank,
+                                  float* gt_score, int32_t* topk_idx, float* topk_score, void* work, int64_t Nq,
+                                  int64_t Ng, int32_t D, int64_t ldq, int64_t ldg, int32_t topk, void* stream) {
+    if (!rt_supported(Nq, Ng, D, topk)) return CLV_ERR_UNSUPPORTED;
+    if (!query || !gallery || !rank || !gt_score || !work || ldq < D || ldg < D) return CLV_ERR_ARG;
+    if (topk > 0 && (!topk_idx || !topk_score)) return CLV_ERR_ARG;
+    if (!gt && Nq > Ng) return CLV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return CLV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const RtPlan p = rt_plan(Nq, Ng);
+    float* qn = (float*)work;
+    float* gn = qn + Nq * (int64_t)D;
+    float* part_score = gn + Ng * (int64_t)D;
+    int32_t* part_idx = (int32_t*)(part_score + (int64_t)p.chunks * Nq * topk);
+    const int64_t rows = Nq + Ng;
+    hipLaunchKernelGGL(retrieval_normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, query, gallery, qn,
+                       Nq, Ng, (int)D, ldq, ldg);
+    hipLaunchKernelGGL(retrieval_score_kernel<RT_GT>, dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, gt, rank, gt_score,
+                       (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0);
+    if (topk > 0) {
+        hipLaunchKernelGGL(retrieval_score_kernel<RT_TOPK>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
+                           gt_score, part_score, part_idx, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, (int)topk);
+        hipLaunchKernelGGL(retrieval_topk_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
+                           part_idx, topk_idx, topk_score, (int)Nq, p.chunks, (int)topk);
+    } else {
+        hipLaunchKernelGGL(retrieval_score_kernel<RT_COUNT>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
+                           gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, 0);
+    }
+    return clv_check_launch();
+}

@@ -2663,3 +2663,40 @@ def attn_probs_mean(qkv, kmask, num_heads):
     check(_lib.lib().clv_attn_probs_mean(_ptr(qkv), _ptr(km), _ptr(out), N, S, num_heads, hd, float(hd) ** -0.5,
                                          _stream()), 'clv_attn_probs_mean')
     return out
+
+
+def retrieval_rank(query, gallery, gt=None, topk=0):
+    """Retrieval ranks on the device (clv_retrieval_rank; accuracy.py:430-462 without the score matrix or the sort).
+    query fp32 [Nq, D], gallery fp32 [Ng, D] (rows are normalised inside, all-zero rows stay zero), gt int [Nq] = each
+    query's ground-truth gallery row (None: query i <-> row i) ->
+    (rank int32 [Nq]: 0-based position of the ground truth in the stable descending order of the query's scores, -1 where
+    gt < 0;  gt_score fp32 [Nq];  topk_idx int32 [Nq, topk] and topk_score fp32 [Nq, topk], or None, None with topk = 0).
+    Inference only: no autograd."""
+    _need_gpu(query, gallery, gt)
+    if query.dtype != torch.float32 or gallery.dtype != torch.float32:
+        raise TypeError(f'retrieval_rank takes fp32 embeddings (got {query.dtype}, {gallery.dtype})')
+    if query.dim() != 2 or gallery.dim() != 2 or query.shape[1] != gallery.shape[1]:
+        raise ValueError(f'retrieval_rank: query [Nq, D] and gallery [Ng, D] (got {tuple(query.shape)}, {tuple(gallery.shape)})')
+    q, g = query.detach(), gallery.detach()
+    q = q if q.stride(1) == 1 or q.shape[1] == 1 else q.contiguous()
+    g = g if g.stride(1) == 1 or g.shape[1] == 1 else g.contiguous()
+    Nq, D = q.shape
+    Ng, topk = g.shape[0], int(topk)
+    if gt is not None:
+        if gt.shape != (Nq,):
+            raise ValueError(f'retrieval_rank: gt must be [{Nq}] (got {tuple(gt.shape)})')
+        gt = _c(gt.detach().to(torch.int32))
+    elif Nq > Ng:
+        raise ValueError(f'retrieval_rank: without gt query i is matched with gallery row i, but Nq = {Nq} > Ng = {Ng}')
+    L = _lib.lib()
+    nbytes = L.clv_retrieval_work_bytes(Nq, Ng, D, topk)
+    check(min(nbytes, 0), 'clv_retrieval_work_bytes')
+    dev = q.device
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    rank = torch.empty(Nq, device=dev, dtype=torch.int32)
+    gscore = torch.empty(Nq, device=dev, dtype=torch.float32)
+    tidx = torch.empty(Nq, topk, device=dev, dtype=torch.int32) if topk else None
+    tscore = torch.empty(Nq, topk, device=dev, dtype=torch.float32) if topk else None
+    check(L.clv_retrieval_rank(_ptr(q), _ptr(g), _ptr(gt), _ptr(rank), _ptr(gscore), _ptr(tidx), _ptr(tscore), _ptr(work),
+                               Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), topk, _stream()), 'clv_retrieval_rank')
+    return rank, gscore, tidx, tscore

@@ -7,9 +7,12 @@
 * ``CloverRunner``: epoch loop, hook call points and the multi-dataloader interleave of
   ``mmaction/core/runner/clover_runner.py:17-35,60-96`` (one optimizer step per loader per batch index), including
   its behaviour once the shorter loader is exhausted;
-* checkpoints in the reference's ``{'meta', 'state_dict', 'optimizer'}`` layout (``epoch_based_runner.py:25-58``).
+* checkpoints in the reference's ``{'meta', 'state_dict', 'optimizer'}`` layout (``epoch_based_runner.py:25-58``);
+* ``EvalHook``: validation during training — schedule, rule inference and best-checkpoint keeping of
+  ``mmaction/core/hooks/my_eval_hook.py:404-880`` (``tools/train.py --validate``, ``tools/train.py:192-209``).
 
-The step itself is ``CloverEngine.step`` (or any object with ``train_step``); nothing here touches the GPU.
+The step itself is ``CloverEngine.step`` (or any object with ``train_step``); nothing here touches the GPU except the
+test loops ``EvalHook`` calls (``clover_amd.evaluation``).
 """
 import ast
 import copy
@@ -191,6 +194,203 @@ class CheckpointHook(Hook):
             runner.save_checkpoint(self.out_dir, f'epoch_{runner.epoch + 1}.pth')
 
 
+
+class EvalHook(Hook):
+    """``MyEvalHook`` + ``MyDistEvalHook`` (my_eval_hook.py:404-880): every ``interval`` epochs (or iterations with
+    ``by_epoch=False``) run the test loop over ``dataloader``, compute the metrics, log them and keep the best checkpoint.
+
+    ``test_fn``: ``'recall_for_video_text_retrieval'`` or None -> ``multi_gpu_test_retrieval`` + ``evaluate_retrieval``
+    (embeddings stay on the device, ranks from ``ops.retrieval_rank``); ``'use_itm_head_fn'`` ->
+    ``multi_gpu_test_itm_finetune`` + ``evaluate_qa``; a callable ``test_fn(model, dataloader)`` returns the metrics dict
+    itself.  EVERY rank runs the test loop (its collection is a collective); rank 0 alone evaluates, appends
+    ``dict(epoch, **metrics)`` to ``records``, prints it through ``printer`` (what ``LogHook`` is given) and saves.
+    The best score and path live in ``runner.meta['hook_msgs']`` (``best_score``, ``best_ckpt``), which checkpoints carry
+    and ``CloverRunner.resume`` restores; the best checkpoint is ``{basename(work_dir)}_best_{key}_epoch_{n}.pth`` and
+    replaces the previous best file (:693-707).
+
+    The test loop runs eagerly between the engine's graph replays, in ``model.eval()`` under ``no_grad``.  An engine-bound
+    model computes from the 16-bit shadows AdamW rewrites in place (``param._clv_shadow``, read per call by ``ops``), so it
+    sees the current weights; the loop feeds its own batches, never the graphs' static inputs, draws no dropout seed
+    (p = 0 in eval mode) and runs no backward, so the first-touch state stays as the last step left it.  ``_guard`` checks
+    those three, and the model's mode, around every evaluation."""
+
+    rule_map = {'greater': lambda x, y: x > y, 'less': lambda x, y: x < y}
+    init_value_map = {'greater': -float('inf'), 'less': float('inf')}
+    _default_greater_keys = ['acc', 'top', 'AR@', 'auc', 'precision', 'mAP', 'mDice', 'mIoU', 'mAcc', 'aAcc', 'Recall@',
+                             'accuracy']
+    _default_less_keys = ['loss']
+
+    def __init__(self, dataloader, start=None, interval=1, by_epoch=True, save_best='auto', rule=None, test_fn=None,
+                 greater_keys=None, less_keys=None, gpu_collect=True, metrics=None, broadcast_bn_buffer=True,
+                 printer=None):
+        if interval <= 0:
+            raise ValueError(f'interval must be a positive number, but got {interval}')
+        assert isinstance(by_epoch, bool), '``by_epoch`` should be a boolean'
+        if start is not None and start < 0:
+            raise ValueError(f'The evaluation start epoch {start} is smaller than 0')
+        assert isinstance(save_best, str) or save_best is None, f'"save_best" should be a str or None, not {type(save_best)}'
+        self.dataloader, self.interval, self.start, self.by_epoch = dataloader, interval, start, by_epoch
+        self.save_best, self.initial_flag = save_best, True
+        if test_fn is not None and not callable(test_fn) and test_fn not in ('recall_for_video_text_retrieval',
+                                                                              'use_itm_head_fn'):
+            raise KeyError(f'test_fn {test_fn!r}: recall_for_video_text_retrieval, use_itm_head_fn or a callable')
+        self.test_fn = test_fn
+        if metrics is None:
+            metrics = ['video_qa_mc'] if test_fn == 'use_itm_head_fn' else ['recall_for_video_text_retrieval']
+        self.metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+        self.gpu_collect, self.broadcast_bn_buffer, self.printer = gpu_collect, broadcast_bn_buffer, printer
+        as_list = lambda k, d: list(d) if k is None else ([k] if isinstance(k, str) else list(k))          # noqa: E731
+        self.greater_keys = as_list(greater_keys, self._default_greater_keys)
+        self.less_keys = as_list(less_keys, self._default_less_keys)
+        self.records, self.best_ckpt_path = [], None
+        if self.save_best is not None:
+            self._init_rule(rule, self.save_best)
+
+    def _init_rule(self, rule, key_indicator):
+        """:534-581 — without a rule: the key (case-insensitive) equal to, else containing, an entry of greater_keys /
+        less_keys, greater first; 'auto' is resolved at the first evaluation from the first metric key."""
+        if rule not in self.rule_map and rule is not None:
+            raise KeyError(f'rule must be greater, less or None, but got {rule}.')
+        if rule is None and key_indicator != 'auto':
+            lc = key_indicator.lower()
+            greater, less = [k.lower() for k in self.greater_keys], [k.lower() for k in self.less_keys]
+            if lc in greater:
+                rule = 'greater'
+            elif lc in less:
+                rule = 'less'
+            elif any(k in lc for k in greater):
+                rule = 'greater'
+            elif any(k in lc for k in less):
+                rule = 'less'
+            else:
+                raise ValueError(f'Cannot infer the rule for key {key_indicator}, thus a specific rule must be specified.')
+        self.rule, self.key_indicator = rule, key_indicator
+        if self.rule is not None:
+            self.compare_func = self.rule_map[self.rule]
+
+    @staticmethod
+    def _rank_world():
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_rank(), dist.get_world_size()
+        return 0, 1
+
+    # ---- call points (:583-616)
+    def before_run(self, runner):
+        if self.save_best is not None:
+            if runner.meta is None:
+                runner.meta = {}
+            runner.meta.setdefault('hook_msgs', {})
+            self.best_ckpt_path = runner.meta['hook_msgs'].get('best_ckpt', None)
+
+    def before_train_iter(self, runner):
+        if self.by_epoch or not self.initial_flag:
+            return
+        if self.start is not None and runner.iter >= self.start:
+            self.after_train_iter(runner)
+        self.initial_flag = False
+
+    def before_train_epoch(self, runner):
+        if not (self.by_epoch and self.initial_flag):
+            return
+        if self.start is not None and runner.epoch >= self.start:
+            self.after_train_epoch(runner)
+        self.initial_flag = False
+
+    def after_train_iter(self, runner):
+        if not self.by_epoch:
+            self._do_evaluate(runner)
+
+    def after_train_epoch(self, runner):
+        if self.by_epoch:
+            self._do_evaluate(runner)
+
+    def _should_evaluate(self, runner):
+        """:631-664."""
+        current = runner.epoch if self.by_epoch else runner.iter
+        if self.start is None:
+            return (current + 1) % self.interval == 0
+        if (current + 1) < self.start:
+            return False
+        return (current + 1 - self.start) % self.interval == 0
+
+    # ---- the evaluation itself (:843-878)
+    @staticmethod
+    def _guard(runner):
+        """What an evaluation must leave alone: the model's mode, and on a CloverEngine the number of captured graph
+        sets, the first-touch marks and the device counter the dropout seeds come from."""
+        eng = runner.stepper
+        state = dict(training=runner.model.training)
+        if hasattr(eng, '_captures'):
+            from . import ops
+            state['captures'] = len(eng._captures)
+            state['first_touch'] = (eng._ft.on, frozenset(eng._ft.done))
+            dev = next(runner.model.parameters()).device
+            if ops._dev_key(dev) in ops._DROPOUT_COUNTER:
+                state['dropout_counter'] = int(ops._dropout_counter(dev).item())
+        return state
+
+    def _test(self, model):
+        from .evaluation import (evaluate_qa, evaluate_retrieval, multi_gpu_test_itm_finetune,
+                                 multi_gpu_test_retrieval)
+        rank, _ = self._rank_world()
+        if callable(self.test_fn):
+            res = self.test_fn(model, self.dataloader)
+            return dict(res) if rank == 0 else None
+        if self.test_fn == 'use_itm_head_fn':
+            res = multi_gpu_test_itm_finetune(model, self.dataloader)
+            return evaluate_qa(res, self.metrics) if rank == 0 else None
+        res = multi_gpu_test_retrieval(model, self.dataloader, gpu_collect=self.gpu_collect, to_host=False)
+        return evaluate_retrieval(res, self.metrics) if rank == 0 else None
+
+    def _do_evaluate(self, runner):
+        rank, world = self._rank_world()
+        if self.broadcast_bn_buffer and world > 1:                    # :850-856, before the schedule check as there
+            import torch.distributed as dist
+            from .nn import BatchNorm1d
+            for m in runner.model.modules():
+                if isinstance(m, BatchNorm1d) and m.track_running_stats:
+                    dist.broadcast(m.running_var, 0)
+                    dist.broadcast(m.running_mean, 0)
+        if not self._should_evaluate(runner):
+            return
+        before = self._guard(runner)
+        eval_res = self._test(runner.model)
+        after = self._guard(runner)
+        if after != before:
+            raise RuntimeError(f'EvalHook: the test loop disturbed the training state: {before} -> {after}')
+        if rank != 0:
+            return
+        when = dict(epoch=runner.epoch + 1) if self.by_epoch else dict(iter=runner.iter + 1)
+        rec = dict(when, mode='val', **{k: float(v) for k, v in eval_res.items()})
+        self.records.append(rec)
+        if self.printer:
+            self.printer(rec)
+        if self.save_best:
+            self._save_ckpt(runner, eval_res)
+
+    def _save_ckpt(self, runner, eval_res):
+        """:666-707 — compare, note best score and path in runner.meta['hook_msgs'], drop the previous best file, save."""
+        current = f'epoch_{runner.epoch + 1}' if self.by_epoch else f'iter_{runner.iter + 1}'
+        if self.key_indicator == 'auto':
+            self._init_rule(self.rule, list(eval_res.keys())[0])
+        key_score = eval_res[self.key_indicator]
+        msgs = runner.meta.setdefault('hook_msgs', {})
+        best_score = msgs.get('best_score', self.init_value_map[self.rule])
+        if not self.compare_func(key_score, best_score):
+            return
+        msgs['best_score'] = float(key_score)
+        if self.best_ckpt_path and os.path.isfile(self.best_ckpt_path):
+            os.remove(self.best_ckpt_path)
+        name = f'{os.path.basename(os.path.normpath(runner.work_dir))}_best_{self.key_indicator}_{current}.pth'
+        self.best_ckpt_path = os.path.join(runner.work_dir, name)
+        msgs['best_ckpt'] = self.best_ckpt_path
+        runner.save_checkpoint(runner.work_dir, name)
+        if self.printer:
+            self.printer(f'Now best checkpoint is saved as {name}. Best {self.key_indicator} is '
+                         f'{float(key_score):0.4f} at {current.replace("_", " ")}')
+
+
 class CloverRunner:
     """``stepper`` is a CloverEngine (``step(batch)``) or a module with ``train_step(batch, optimizer)``."""
 
@@ -316,4 +516,8 @@ class CloverRunner:
         self.iter = ckpt['meta'].get('iter', 0)
         if 'optimizer' in ckpt and hasattr(self.stepper, 'load_optimizer_state'):
             self.stepper.load_optimizer_state(ckpt['optimizer'])
+        # mmcv's resume: what hooks noted in the checkpoint (EvalHook: best_score / best_ckpt) carries over, so the
+        # resumed run keeps comparing against the best score so far
+        if ckpt['meta'].get('hook_msgs'):
+            self.meta.setdefault('hook_msgs', {}).update(ckpt['meta']['hook_msgs'])
         return ckpt

@@ -654,6 +654,23 @@ int clv_qa_choice_assemble_bwd(const void* dfeat, void* dvisual, void* dtext, in
 int clv_attn_probs_mean(const void* qkv, const float* kmask, float* out, int32_t N, int32_t S, int32_t nH, int32_t hd,
                         float scale, void* stream);
 
+/* Text -> video retrieval ranks without the score matrix (the metric of mmaction/core/evaluation/accuracy.py:430-462 with
+ * normalize_fn of mmaction/utils/numpy_norm.py:5-8).  query fp32 [Nq][D] (row stride ldq), gallery fp32 [Ng][D] (ldg): rows
+ * are scaled to unit L2 norm (IEEE sqrt and division; an all-zero row stays zero), s[i][j] = q_i . g_j on the exact-f32
+ * MFMA 16x16x4.  gt int32 [Nq]: the gallery row that is query i's ground truth (NULL: gt[i] = i, needs Nq <= Ng).
+ *   rank[i]     = #{j : s[i][j] > s[i][g]} + #{j < g : s[i][j] == s[i][g]}: the 0-based position of g = gt[i] in the STABLE
+ *                 descending order of row i (j == g is excluded by index); -1 where gt[i] < 0 or gt[i] >= Ng
+ *   gt_score[i] = s[i][g] (NaN where rank[i] = -1)
+ *   topk_idx / topk_score [Nq][topk] (topk 1..16; 0 = off, both may be NULL): the first topk entries of that same order,
+ *                 padded with -1 / -inf when Ng < topk.
+ * work: clv_retrieval_work_bytes(...) bytes, 16-byte aligned; nothing is allocated inside, every launch goes to `stream`
+ * (capturable).  D % 4 == 0, 4 <= D <= 4096, topk <= 16, Nq, Ng >= 1, else CLV_ERR_UNSUPPORTED (the size query returns the
+ * same code).  Results are deterministic: counts meet through int32 adds. */
+int64_t clv_retrieval_work_bytes(int64_t Nq, int64_t Ng, int32_t D, int32_t topk);
+int clv_retrieval_rank(const float* query, const float* gallery, const int32_t* gt, int32_t* rank, float* gt_score,
+                       int32_t* topk_idx, float* topk_score, void* work, int64_t Nq, int64_t Ng, int32_t D, int64_t ldq,
+                       int64_t ldg, int32_t topk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,33 +34,14 @@ def parse_args():
                    help='evaluation metrics (default: recall_for_video_text_retrieval; video-QA configs: their '
                         'evaluation.metrics)')
     p.add_argument('--gpu-collect', action='store_true', help='accepted for CLI compatibility (collection is always RCCL)')
+    p.add_argument('--topk', type=int, default=0,
+                   help='retrieval only: score on the device and add the K best video indices per query to --out (1..16)')
     p.add_argument('--cfg-options', nargs='+', default=[], help='a.b=c overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher')
     return p.parse_args()
 
 
-class SyntheticTestLoader:
-    """This rank's shard of a synthetic test set: batches with ``index`` as the reference's test pipeline emits."""
-
-    def __init__(self, pairs, batch, frames, tokens, rank, world, device, seed=4242, qa=None):
-        import bench
-        from clover_amd.utils.qa_synthetic import qa_batch
-        self.batches = []
-        mine = list(range(rank, pairs, world))
-        keys = ('imgs', 'token_ids', 'segment_ids', 'input_mask') + (('label',) if qa is not None else ())
-        for s in range(0, len(mine), batch):
-            idx = mine[s:s + batch]
-            b = (qa_batch(len(idx), tokens, frames, seed + idx[0], **qa) if qa is not None
-                 else bench.synthetic_batch(len(idx), frames, tokens, seed + idx[0]))
-            b = {k: b[k].to(device) for k in keys}
-            b['index'] = torch.tensor(idx, device=device)
-            self.batches.append(b)
-
-    def __len__(self):
-        return len(self.batches)
-
-    def __iter__(self):
-        return iter(self.batches)
+from clover_amd.utils.synthetic_loaders import SyntheticTestLoader      # noqa: E402,F401 (exported from here too)
 
 
 def select_test(cfg, eval_metrics):
@@ -87,6 +68,8 @@ def main():
     cfg = Config.fromfile(args.config)
     cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
     kind, metrics = select_test(cfg, args.eval)
+    if args.topk and (kind != 'retrieval' or not 1 <= args.topk <= 16):
+        raise SystemExit('--topk K: the retrieval test only, K in 1..16')
     if not torch.cuda.is_available():
         raise SystemExit('tools/test.py needs an MI355X (no CPU fallback)')
     if args.launcher == 'none':
@@ -116,14 +99,21 @@ def main():
     if kind == 'qa':
         results = multi_gpu_test_itm_finetune(model, loader)
     else:
-        results = multi_gpu_test_retrieval(model, loader)
+        results = multi_gpu_test_retrieval(model, loader, to_host=not args.topk)
     if rank == 0:
-        metrics = (evaluate_qa if kind == 'qa' else evaluate_retrieval)(results, metrics)
+        if args.topk:                                     # ranks and the K best videos per query from the device
+            metrics = evaluate_retrieval(results, metrics, topk=args.topk)
+        else:
+            metrics = (evaluate_qa if kind == 'qa' else evaluate_retrieval)(results, metrics)
+        topk = metrics.pop('topk', None)
         for k, v in metrics.items():
             print(f'{k}: {v:.04f}')                                                   # tools/test.py:255-256
         if args.out:
+            out = dict(metrics={k: float(v) for k, v in metrics.items()}, pairs=int(len(results['index'])))
+            if topk is not None:
+                out['topk'] = topk.tolist()
             with open(args.out, 'w') as f:
-                json.dump(dict(metrics={k: float(v) for k, v in metrics.items()}, pairs=int(len(results['index']))), f)
+                json.dump(out, f)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -24,6 +24,8 @@ def parse_args():
     p.add_argument('--work_dir', help='the dir to save logs and models')
     p.add_argument('--resume-from', help='the checkpoint file to resume from')
     p.add_argument('--load-from', help='the checkpoint file to load from')
+    p.add_argument('--validate', action='store_true',
+                   help='whether to evaluate the checkpoint during training (cfg.evaluation over data.synthetic_test)')
     p.add_argument('--seed', type=int, default=None, help='random seed')
     p.add_argument('--cfg-options', nargs='+', default=[], help='a.b=c overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='pytorch', help='job launcher')
@@ -54,8 +56,8 @@ class SyntheticLoader:
 
 def main():
     args = parse_args()
-    from clover_amd.runner import (CheckpointHook, CloverRunner, Config, LogHook, LrUpdaterHook, parse_cfg_options,
-                                   scaled_lr)
+    from clover_amd.runner import (CheckpointHook, CloverRunner, Config, EvalHook, LogHook, LrUpdaterHook,
+                                   parse_cfg_options, scaled_lr)
     import clover_amd
     from clover_amd.engine import CloverEngine
 
@@ -111,6 +113,14 @@ def main():
         runner.register_hook(LogHook(cfg.get('log_config', {}).get('interval', 10), printer=print))
         if cfg.get('checkpoint_config'):
             runner.register_hook(CheckpointHook(cfg.work_dir, cfg.checkpoint_config.get('interval', 1)))
+    if args.validate:                                    # tools/train.py:192-209 — on EVERY rank: the collection is a collective
+        from clover_amd.utils.synthetic_loaders import SyntheticTestLoader
+        ev = dict(cfg.get('evaluation') or {})
+        st = cfg.data.get('synthetic_test', dict(pairs=64, frames=8, tokens=32))
+        qa = st.get('qa') if ev.get('test_fn') == 'use_itm_head_fn' else None
+        val = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
+                                  st.get('tokens', 32), rank, world, dev, qa=qa)
+        runner.register_hook(EvalHook(val, printer=print if rank == 0 else None, **ev))
     if args.resume_from:
         runner.resume(args.resume_from)
     elif args.load_from:
