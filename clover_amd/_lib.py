@@ -187,6 +187,8 @@ SIGNATURES = {
     'clv_qa_choice_assemble_bwd': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
     'clv_retrieval_work_bytes': (C.c_int64, [_i64, _i64, _i32, _i32]),
     'clv_retrieval_rank': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _i32, _p]),
+    'clv_retrieval_group_work_bytes': (C.c_int64, [_i64, _i64, _i32]),
+    'clv_retrieval_group_best': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _f, _p]),
 }
 
 _lib = None

@@ -23,6 +23,14 @@
 //      (score descending, index ascending).
 // Padded rows and columns (Nq, Ng not multiples of 64; D not a multiple of 16) are staged as zeros and masked by index
 // in every epilogue: they never count and never enter a list.
+//
+// clv_retrieval_group_best (zero-shot multiple choice, accuracy.py:396-427; the video -> text direction of a many-caption
+// test set) asks another question of the same scores: the best gallery row inside a per-query range [lo, hi), without
+// the N x C N matrix whose block diagonal the reference keeps.  retrieval_score_kernel<RT_BEST> is pass 3's tile loop
+// over the tiles that meet the ranges of the workgroup's 64 queries; the tile's scores pass through LDS as for top-K and
+// one thread per query keeps the first maximum of its range.  retrieval_best_merge_kernel joins the chunks; the rank of
+// that row in the whole gallery, when asked for, is passes 2 and 3 with gt = best_idx.  Rows are scaled by
+// 1 / max(norm, eps) (sim_matrix, accuracy.py:385-394); eps = 0 is the normalisation above.
 #include "common.hpp"
 #include "../../include/clover_hip.h"
 
@@ -37,7 +45,8 @@ constexpr int RT_KMAX = 16, RT_LLD = RT_KMAX + 1;
 constexpr int RT_MAX_CHUNKS = 64;          // bounds the top-K partial table: chunks x Nq x K x 8 bytes
 constexpr int RT_WANT_GROUPS = 512;        // two workgroups per CU before the gallery stops being split
 
-enum { RT_GT = 0, RT_COUNT = 1, RT_TOPK = 2 };
+enum { RT_GT = 0, RT_COUNT = 1, RT_TOPK = 2, RT_BEST = 3 };
+constexpr const int32_t* RT_ALL = nullptr;   // lo / hi of the modes that have no ranges
 
 struct RtPlan {
     int nqb, tiles, tiles_per_chunk, chunks;
@@ -59,28 +68,33 @@ inline RtPlan rt_plan(int64_t Nq, int64_t Ng) {
 __global__ void __launch_bounds__(256) retrieval_normalize_kernel(const float* __restrict__ query,
                                                                   const float* __restrict__ gallery,
                                                                   float* __restrict__ out, int64_t Nq, int64_t Ng, int D,
-                                                                  int64_t ldq, int64_t ldg) {
+                                                                  int64_t ldq, int64_t ldg, float eps) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= Nq + Ng) return;
     const float* e = row < Nq ? query + row * ldq : gallery + (row - Nq) * ldg;
     float s = 0.f;
     for (int d = lane; d < D; d += 64) s += e[d] * e[d];
-    float nrm = sqrtf(wave_sum(s));
+    float nrm = fmaxf(sqrtf(wave_sum(s)), eps);             // accuracy.py:391 — max(norm, eps); eps = 0 changes nothing
     if (nrm == 0.f) nrm = 1.f;                              // numpy_norm.py:7 — l2[l2 == 0] = 1
     float* o = out + row * D;
     for (int d = lane; d < D; d += 64) o[d] = e[d] / nrm;
 }
 
 // qn [Nq][D], gn [Ng][D] packed unit rows.  Grid: (query blocks, gallery chunks); RT_GT: (query blocks, 1).
+// RT_BEST reads lo / hi [Nq] (both null: the whole gallery) and writes part_score / part_idx [chunks][Nq]: the first
+// maximum of query m over the columns of this chunk inside [lo[m], hi[m]), or -inf / -1 when there is none.
 template <int MODE>
 __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __restrict__ qn, const float* __restrict__ gn,
                                                               const int32_t* __restrict__ gt, int32_t* __restrict__ rank,
                                                               float* __restrict__ gt_score, float* __restrict__ part_score,
                                                               int32_t* __restrict__ part_idx, int Nq, int Ng, int D,
-                                                              int tiles_per_chunk, int topk) {
+                                                              int tiles_per_chunk, int topk,
+                                                              const int32_t* __restrict__ lo,
+                                                              const int32_t* __restrict__ hi) {
     __shared__ float As[RT_BM * RT_LD], Bs[RT_BN * RT_LD];
-    __shared__ float Ss[MODE == RT_TOPK ? RT_BM * RT_SLD : 1];
+    __shared__ float Ss[(MODE == RT_TOPK || MODE == RT_BEST) ? RT_BM * RT_SLD : 1];
+    __shared__ int Span[MODE == RT_BEST ? 2 : 1];
     __shared__ float Ls[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
     __shared__ int32_t Li[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -101,7 +115,7 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
     // per-lane view of the accumulators: acc[i][j][r] = s[m0 + wr + i*16 + lg*4 + r][n0 + wc + j*16 + lr]
     float gs[2][4];
     int g[2][4], cnt[2][4];
-    if (MODE != RT_GT) {
+    if (MODE == RT_COUNT || MODE == RT_TOPK) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -119,8 +133,36 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
         }
     }
 
-    const int tile0 = MODE == RT_GT ? 0 : blockIdx.y * tiles_per_chunk;
-    const int tile1 = MODE == RT_GT ? 1 : min(tile0 + tiles_per_chunk, (Ng + RT_BN - 1) / RT_BN);
+    // RT_BEST: thread t < 64 (wave 0) owns query m0 + t; a range that is empty or leaves [0, Ng] holds no column
+    int qlo = 0, qhi = 0, bidx = -1;
+    float bscore = -INFINITY;
+    if (MODE == RT_BEST) {
+        if (tid < RT_BM) {
+            if (m0 + tid < Nq) {
+                qlo = lo ? lo[m0 + tid] : 0;
+                qhi = hi ? hi[m0 + tid] : Ng;
+                if (qlo < 0 || qhi > Ng || qlo >= qhi) qlo = qhi = 0;
+            }
+            int smin = qlo < qhi ? qlo : 0x7fffffff, smax = qlo < qhi ? qhi : 0;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                smin = min(smin, __shfl_xor(smin, o, 64));
+                smax = max(smax, __shfl_xor(smax, o, 64));
+            }
+            if (tid == 0) {
+                Span[0] = smin;
+                Span[1] = smax;
+            }
+        }
+        __syncthreads();
+    }
+
+    int tile0 = MODE == RT_GT ? 0 : blockIdx.y * tiles_per_chunk;
+    int tile1 = MODE == RT_GT ? 1 : min(tile0 + tiles_per_chunk, (Ng + RT_BN - 1) / RT_BN);
+    if (MODE == RT_BEST) {                                    // only the tiles that meet [min lo, max hi) of the 64 queries
+        tile0 = max(tile0, Span[0] / RT_BN);
+        tile1 = min(tile1, (Span[1] + RT_BN - 1) / RT_BN);
+    }
     for (int tile = tile0; tile < tile1; ++tile) {
         const int n0 = tile * RT_BN;
         const float* bsrc;
@@ -181,6 +223,27 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
                         }
                     }
             }
+        } else if (MODE == RT_BEST) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        Ss[(wr + i * 16 + lg * 4 + r) * RT_SLD + wc + j * 16 + lr] = acc[i][j][r];
+            __syncthreads();
+            if (tid < RT_BM) {
+                // ascending columns, strict >: the first maximum.  qhi <= Ng keeps the padded columns out.
+                const int c1 = min(RT_BN, qhi - n0);
+                for (int c = max(0, qlo - n0); c < c1; ++c) {
+                    const float s = Ss[tid * RT_SLD + c];
+                    if (bidx < 0 || s > bscore) {
+                        bscore = s;
+                        bidx = n0 + c;
+                    }
+                }
+            }
+            // the next tile writes Ss only after the syncs of its k loop (D >= 4: at least one step)
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -222,7 +285,13 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
         }
     }
 
-    if (MODE != RT_GT) {
+    if (MODE == RT_BEST) {
+        if (tid < RT_BM && m0 + tid < Nq) {
+            part_score[(int64_t)blockIdx.y * Nq + m0 + tid] = bscore;
+            part_idx[(int64_t)blockIdx.y * Nq + m0 + tid] = bidx;
+        }
+    }
+    if (MODE == RT_COUNT || MODE == RT_TOPK) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -290,6 +359,29 @@ __global__ void __launch_bounds__(256) retrieval_topk_merge_kernel(const float* 
     }
 }
 
+// one thread per query: the best of its chunk partials in the order (score descending, index ascending); -1 / NaN when
+// no chunk held a column of the query's range.
+__global__ void __launch_bounds__(256) retrieval_best_merge_kernel(const float* __restrict__ part_score,
+                                                                   const int32_t* __restrict__ part_idx,
+                                                                   int32_t* __restrict__ best_idx,
+                                                                   float* __restrict__ best_score, int Nq, int chunks) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Nq) return;
+    float bs = 0.f;
+    int bi = -1;
+    for (int c = 0; c < chunks; ++c) {
+        const int ci = part_idx[(int64_t)c * Nq + i];
+        if (ci < 0) continue;
+        const float cs = part_score[(int64_t)c * Nq + i];
+        if (bi < 0 || cs > bs || (cs == bs && ci < bi)) {
+            bs = cs;
+            bi = ci;
+        }
+    }
+    best_idx[i] = bi;
+    best_score[i] = bi >= 0 ? bs : __builtin_nanf("");
+}
+
 inline bool rt_supported(int64_t Nq, int64_t Ng, int32_t D, int32_t topk) {
     return Nq >= 1 && Ng >= 1 && Nq <= 0x7fffffff - RT_BM && Ng <= 0x7fffffff - RT_BN && D >= 4 && D <= 4096 &&
            D % 4 == 0 && topk >= 0 && topk <= RT_KMAX;
@@ -319,17 +411,59 @@ extern "C" int clv_retrieval_rank(const float* query, const float* gallery, cons
     int32_t* part_idx = (int32_t*)(part_score + (int64_t)p.chunks * Nq * topk);
     const int64_t rows = Nq + Ng;
     hipLaunchKernelGGL(retrieval_normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, query, gallery, qn,
-                       Nq, Ng, (int)D, ldq, ldg);
+                       Nq, Ng, (int)D, ldq, ldg, 0.f);
     hipLaunchKernelGGL(retrieval_score_kernel<RT_GT>, dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, gt, rank, gt_score,
-                       (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0);
+                       (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0, RT_ALL, RT_ALL);
     if (topk > 0) {
         hipLaunchKernelGGL(retrieval_score_kernel<RT_TOPK>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
-                           gt_score, part_score, part_idx, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, (int)topk);
+                           gt_score, part_score, part_idx, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, (int)topk, RT_ALL,
+                           RT_ALL);
         hipLaunchKernelGGL(retrieval_topk_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
                            part_idx, topk_idx, topk_score, (int)Nq, p.chunks, (int)topk);
     } else {
         hipLaunchKernelGGL(retrieval_score_kernel<RT_COUNT>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
-                           gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, 0);
+                           gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, 0,
+                           RT_ALL, RT_ALL);
+    }
+    return clv_check_launch();
+}
+
+extern "C" int64_t clv_retrieval_group_work_bytes(int64_t Nq, int64_t Ng, int32_t D) {
+    if (!rt_supported(Nq, Ng, D, 0)) return CLV_ERR_UNSUPPORTED;
+    const RtPlan p = rt_plan(Nq, Ng);
+    return (Nq + Ng) * (int64_t)D * 4 + (int64_t)p.chunks * Nq * 8;
+}
+
+extern "C" int clv_retrieval_group_best(const float* query, const float* gallery, const int32_t* lo, const int32_t* hi,
+                                        int32_t* best_idx, float* best_score, int32_t* rank, void* work, int64_t Nq,
+                                        int64_t Ng, int32_t D, int64_t ldq, int64_t ldg, float eps, void* stream) {
+    if (!rt_supported(Nq, Ng, D, 0)) return CLV_ERR_UNSUPPORTED;
+    if (!query || !gallery || !best_idx || !best_score || !work || ldq < D || ldg < D) return CLV_ERR_ARG;
+    if ((lo == nullptr) != (hi == nullptr) || !(eps >= 0.f)) return CLV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return CLV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const RtPlan p = rt_plan(Nq, Ng);
+    float* qn = (float*)work;
+    float* gn = qn + Nq * (int64_t)D;
+    float* part_score = gn + Ng * (int64_t)D;
+    int32_t* part_idx = (int32_t*)(part_score + (int64_t)p.chunks * Nq);
+    const int64_t rows = Nq + Ng;
+    hipLaunchKernelGGL(retrieval_normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, query, gallery, qn,
+                       Nq, Ng, (int)D, ldq, ldg, eps);
+    hipLaunchKernelGGL(retrieval_score_kernel<RT_BEST>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn,
+                       (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, part_score, part_idx, (int)Nq, (int)Ng,
+                       (int)D, p.tiles_per_chunk, 0, lo, hi);
+    hipLaunchKernelGGL(retrieval_best_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
+                       part_idx, best_idx, best_score, (int)Nq, p.chunks);
+    if (rank) {
+        // clv_retrieval_rank's passes 2 and 3 with gt = best_idx.  Pass 2 rewrites best_score with s[i][best_idx[i]]: the
+        // same two rows in the same k order, so the same bits (and NaN where best_idx = -1).
+        hipLaunchKernelGGL(retrieval_score_kernel<RT_GT>, dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, (const int32_t*)best_idx,
+                           rank, best_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0, RT_ALL,
+                           RT_ALL);
+        hipLaunchKernelGGL(retrieval_score_kernel<RT_COUNT>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn,
+                           (const int32_t*)best_idx, rank, best_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng,
+                           (int)D, p.tiles_per_chunk, 0, RT_ALL, RT_ALL);
     }
     return clv_check_launch();
 }

@@ -7,6 +7,11 @@ code here too — the device work is the two encoders that produce the embedding
 
 ``recall_on_device`` is the same metric for callers that evaluate inside a training job (runner.EvalHook): the ranks
 come from ``ops.retrieval_rank`` (csrc/retrieval.hip — no score matrix, no sort) and only they cross to the host.
+
+Zero-shot multiple choice (``acc_for_msrvtt_mc``, accuracy.py:396-427) and the many-caption protocol
+(``recall_for_video_text_retrieval_varied``, accuracy.py:465-523, with its test loop my_eval_hook.py:115-215) are here the
+same way: a numpy restatement for host results, and ``mc_acc_on_device`` / ``recall_varied_on_device`` on
+``ops.retrieval_group_best`` / ``ops.retrieval_rank`` for device results.
 """
 import numpy as np
 
@@ -73,18 +78,124 @@ def recall_on_device(video_embd, text_embd, gt=None, topk=0):
     return metrics
 
 
+def sim_matrix(a, b, eps=1e-8):
+    """Cosine scores with rows scaled by 1 / max(norm, eps) (accuracy.py:385-394), in the inputs' precision."""
+    a, b = np.asarray(a), np.asarray(b)
+    a_n = np.maximum(np.linalg.norm(a, axis=1, keepdims=True), eps).astype(a.dtype)
+    b_n = np.maximum(np.linalg.norm(b, axis=1, keepdims=True), eps).astype(b.dtype)
+    return np.dot(a / a_n, (b / b_n).T)
+
+
+def _recall_keys(ind, prefix=''):
+    return {f'{prefix}Recall@1': float(np.sum(ind == 0)) / len(ind) * 100,
+            f'{prefix}Recall@5': float(np.sum(ind < 5)) / len(ind) * 100,
+            f'{prefix}Recall@10': float(np.sum(ind < 10)) / len(ind) * 100,
+            f'{prefix}MR': np.median(ind) + 1}
+
+
+def acc_for_msrvtt_mc(video_embd, text_embd, label, use_sim=True):
+    """MSRVTT / LSMDC multiple choice (accuracy.py:396-427): ``video_embd`` [N, D], ``text_embd`` [N * C, D] (video i's
+    candidates are rows i*C .. i*C + C - 1), ``label`` [N] in [0, C) -> ``{'acc'}``, the float32 mean of
+    ``argmax == label``.  The full [N, N * C] matrix, its (b_v, b_v, ans_num) reshape and the diagonal are kept as there
+    (:413-418); ``use_sim`` selects ``sim_matrix`` (what ``evaluate`` passes, video_dataset.py:182) over the plain dot.
+    The first of equal candidates wins (``argmax``).  The reference's prints and its two ``np.save`` calls are left out."""
+    video_embd, text_embd = _host(video_embd), _host(text_embd)
+    b_v = video_embd.shape[0]
+    text_embd = text_embd.reshape(-1, video_embd.shape[-1])
+    scores = sim_matrix(video_embd, text_embd) if use_sim else np.dot(video_embd, text_embd.T)
+    ans_num = scores.shape[1] // b_v
+    scores = scores.reshape(b_v, b_v, ans_num)
+    ans_diag = np.diagonal(scores, axis1=0, axis2=1).T                                # (C, N) -> (N, C)
+    ans = np.argmax(ans_diag, axis=-1)
+    label = _host_int(label).reshape(-1)
+    return {'acc': float((ans == label).astype(np.float32).mean())}
+
+
+def recall_for_video_text_retrieval_varied(video_embd, text_embd, tid):
+    """Text -> video R@1 / R@5 / R@10 (percent) and median rank (1-based) when video i has ``len(tid[i])`` captions
+    (accuracy.py:465-523): ``text_embd`` [sum of the lengths, D] holds the captions video by video, every caption's ground
+    truth is its video; scores by ``sim_matrix``.  Of ``tid`` only the per-video lengths are used (an int sequence of
+    counts is taken as it is).  No ``Recall@all``, as there.  Equal scores rank by video index (a stable sort, which
+    is also the device path's rule; the reference's ``np.argsort`` leaves their order open)."""
+    counts = np.array([t if np.ndim(t) == 0 else len(t) for t in tid], dtype=np.int64)
+    scores = sim_matrix(_host(text_embd), _host(video_embd))
+    order = np.argsort(-scores, axis=1, kind='stable')
+    gt = np.repeat(np.arange(len(counts)), counts)
+    ind = np.where(order == gt[:, None])[1]
+    return _recall_keys(ind)
+
+
+def mc_acc_on_device(video_embd, text_embd, label, return_pred=False):
+    """``acc_for_msrvtt_mc`` with the scoring on the device: one ``ops.retrieval_group_best`` call in which video i
+    looks at the text rows [i*C, (i+1)*C) only (``eps = 1e-8`` as ``sim_matrix``), so of the N x N*C scores the reference
+    computes only the N x C it keeps are; ``pred = best_idx - i*C`` [N] is all that crosses to the host.  ``text_embd``
+    fp32 [N, C, D] or [N*C, D].  -> ``{'acc'}`` (the float32 mean, as there), with ``return_pred`` also ``'pred'``."""
+    import torch
+    from .. import ops
+    v, t = torch.as_tensor(video_embd).float(), torch.as_tensor(text_embd).float()
+    N = v.shape[0]
+    t = t.reshape(-1, v.shape[-1])
+    if t.shape[0] % N:
+        raise ValueError(f'{t.shape[0]} candidate captions for {N} videos')
+    C = t.shape[0] // N
+    lo = torch.arange(N, device=v.device, dtype=torch.int32) * C
+    best, _, _ = ops.retrieval_group_best(v, t, lo, lo + C, eps=1e-8)
+    pred = (best - lo).cpu().numpy()
+    out = {'acc': float((pred == _host_int(label).reshape(-1)).astype(np.float32).mean())}
+    if return_pred:
+        out['pred'] = pred
+    return out
+
+
+def recall_varied_on_device(video_embd, text_embd, counts, v2t=False):
+    """``recall_for_video_text_retrieval_varied`` with the scoring on the device.  ``video_embd`` fp32 [N, D],
+    ``text_embd`` [sum(counts), D] video by video, ``counts`` int [N].  Text -> video (the reference's four keys) comes
+    from ``ops.retrieval_rank`` with ``gt = repeat_interleave(arange(N), counts)``; rows are normalised as ``normalize_fn``
+    there (``sim_matrix`` differs only for rows of norm below 1e-8).
+
+    With ``v2t`` the result also holds ``V2T_Recall@1/5/10`` and ``V2T_MR``: per video the rank, among all texts, of the
+    best of its own captions (``ops.retrieval_group_best(video, text, lo, hi, want_rank=True)``, the ranges from
+    ``cumsum(counts)``).  That is the usual best-caption protocol of video -> text retrieval (the minimum rank over a
+    video's valid descriptions); it has NO counterpart in the reference, whose function scores text -> video only.
+    Only the int32 rank vectors cross to the host."""
+    import torch
+    from .. import ops
+    v, t = torch.as_tensor(video_embd).float(), torch.as_tensor(text_embd).float()
+    counts = torch.as_tensor(counts).to(device=v.device, dtype=torch.int64).reshape(-1)
+    if counts.shape[0] != v.shape[0] or int(counts.sum()) != t.shape[0]:
+        raise ValueError(f'counts [{counts.shape[0]}] summing to {int(counts.sum())} for {v.shape[0]} videos and '
+                         f'{t.shape[0]} texts')
+    gt = torch.repeat_interleave(torch.arange(v.shape[0], device=v.device), counts).to(torch.int32)
+    rank, _, _, _ = ops.retrieval_rank(t, v, gt=gt)
+    out = _recall_keys(rank.cpu().numpy())
+    if v2t:
+        hi = torch.cumsum(counts, 0)
+        _, _, vrank = ops.retrieval_group_best(v, t, hi - counts, hi, want_rank=True)
+        ind = vrank.cpu().numpy()
+        out.update(_recall_keys(ind[ind >= 0], 'V2T_'))
+    return out
+
+
+def _host_int(x):
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
 def _host(x):
     if hasattr(x, 'detach'):
         x = x.detach().float().cpu().numpy()
     return np.asarray(x)
 
 
-def multi_gpu_test_retrieval(model, data_loader, gpu_collect=True, to_host=True):
+def multi_gpu_test_retrieval(model, data_loader, gpu_collect=True, to_host=True, with_label=False):
     """Embed a test set with ``forward_test(separate_test=True)`` on every rank and collect the embeddings on all
     ranks in dataset order (mmaction/core/hooks/my_eval_hook.py:20-100).  Each batch carries ``index`` (the
     samples' positions in the test set); several clips per sample are averaged, several captions per video are
     grouped, as there (:58-63).  Returns ``dict(video_embd=[N x D], text_embd=[N x ...])`` of numpy arrays, or with
     ``to_host=False`` the same collected, de-duplicated tensors still on the device (for ``recall_on_device``).
+    ``with_label`` (multiple choice): the batches' ``label`` [B] travels with the embeddings — ordered and de-duplicated
+    like them — into ``results['label']`` (the reference reads it from the metas, video_dataset.py:176).
 
     Collection is one ``all_gather`` of the stacked per-rank embeddings (+ indices) instead of the reference's
     pickle-through-uint8-tensor exchange; a 1-rank run has nothing to collect."""
@@ -92,13 +203,17 @@ def multi_gpu_test_retrieval(model, data_loader, gpu_collect=True, to_host=True)
     import torch.distributed as dist
     was_training = model.training
     model.eval()
-    vids, txts, idxs = [], [], []
+    vids, txts, idxs, labels = [], [], [], []
     with torch.no_grad():
         for data in data_loader:
             data = dict(data)
             idxs.append(data.pop('index').reshape(-1).to(torch.int64))
             data.pop('img_metas', None)
-            data.pop('label', None)
+            label = data.pop('label', None)
+            if with_label:
+                if label is None:
+                    raise KeyError('with_label: the batch has no label')
+                labels.append(label.reshape(-1).to(torch.int64))
             v, t = model(return_loss=False, **data)
             if v.shape[0] > t.shape[0]:                                               # :58-60
                 v = v.view(t.shape[0], -1, t.shape[1]).mean(dim=1)
@@ -108,6 +223,7 @@ def multi_gpu_test_retrieval(model, data_loader, gpu_collect=True, to_host=True)
             txts.append(t.float())
     model.train(was_training)
     v, t, ix = torch.cat(vids), torch.cat(txts), torch.cat(idxs).to(vids[0].device)
+    lb = torch.cat(labels).to(v.device) if with_label else None
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         W = dist.get_world_size()
         n = torch.tensor([v.shape[0]], device=v.device)
@@ -122,28 +238,108 @@ def multi_gpu_test_retrieval(model, data_loader, gpu_collect=True, to_host=True)
             dist.all_gather(out, pad)
             return torch.cat([o[:int(k.item())] for o, k in zip(out, ns)])
         v, t, ix = gather(v), gather(t), gather(ix)
+        lb = gather(lb) if with_label else None
     # dataset order; a DistributedSampler pads the last ranks with repeated samples: keep the first of each index
     order = torch.argsort(ix, stable=True)
     ix, v, t = ix[order], v[order], t[order]
     keep = torch.ones_like(ix, dtype=torch.bool)
     keep[1:] = ix[1:] != ix[:-1]
-    if not to_host:
-        return dict(video_embd=v[keep], text_embd=t[keep], index=ix[keep])
-    return dict(video_embd=v[keep].cpu().numpy(), text_embd=t[keep].cpu().numpy(), index=ix[keep].cpu().numpy())
+    res = dict(video_embd=v[keep], text_embd=t[keep], index=ix[keep])
+    if with_label:
+        res['label'] = lb[order][keep]
+    return res if not to_host else {k: x.cpu().numpy() for k, x in res.items()}
 
 
-def evaluate_retrieval(results, metrics=('recall_for_video_text_retrieval',), topk=0):
-    """The retrieval branch of ``VideoDataset.evaluate`` (mmaction/datasets/video_dataset.py:189-195).  Results that
-    hold device tensors (``multi_gpu_test_retrieval(to_host=False)``) are scored on the device (``recall_on_device``,
-    which is also what ``topk`` needs); numpy results take the reference's host path."""
+def multi_gpu_test_retrieval_varied(model, data_loader, to_host=True):
+    """The test loop of a set whose videos have several captions each, in unequal numbers (my_eval_hook.py:115-215): every
+    batch is ONE video (``index`` [1]) with its c_i captions (``token_ids`` [1, c_i, L]), as the reference's loop assumes
+    (:150-164); the clips of the video are averaged (:162-164).  Returns ``video_embd`` [N, D], the flat ``text_embd``
+    [sum c_i, D] video by video and ``counts`` [N] (what the reference keeps as one name list per video, :150-152), plus
+    ``index`` — numpy arrays, or device tensors with ``to_host=False``.  Collected over the ranks with the padded
+    all-gather of ``multi_gpu_test_retrieval`` (texts padded to the longest rank's total), ordered by ``index`` and
+    de-duplicated."""
+    import torch
+    import torch.distributed as dist
+    was_training = model.training
+    model.eval()
+    vids, txts, idxs, cnts = [], [], [], []
+    with torch.no_grad():
+        for data in data_loader:
+            data = dict(data)
+            ix = data.pop('index').reshape(-1).to(torch.int64)
+            if ix.numel() != 1:
+                raise ValueError(f'the varied test loop takes one video per batch (got index {ix.tolist()})')
+            data.pop('img_metas', None)
+            data.pop('label', None)
+            v, t = model(return_loss=False, **data)
+            v = v.unsqueeze(0) if v.dim() == 1 else v                                 # :158-159
+            t = t.reshape(-1, t.shape[-1])                                            # :160-161, flat instead of [1, c, D]
+            if v.shape[0] > 1:                                                        # :162-164
+                v = v.mean(dim=0, keepdim=True)
+            idxs.append(ix)
+            vids.append(v.float())
+            txts.append(t.float())
+            cnts.append(t.shape[0])
+    model.train(was_training)
+    dev = vids[0].device
+    v, t, ix = torch.cat(vids), torch.cat(txts), torch.cat(idxs).to(dev)
+    c = torch.tensor(cnts, device=dev, dtype=torch.int64)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        W = dist.get_world_size()
+
+        def gather(x):
+            n = torch.tensor([x.shape[0]], device=dev)
+            ns = [torch.zeros_like(n) for _ in range(W)]
+            dist.all_gather(ns, n)
+            pad = x.new_zeros((int(max(k.item() for k in ns)),) + tuple(x.shape[1:]))
+            pad[:x.shape[0]] = x
+            out = [torch.empty_like(pad) for _ in range(W)]
+            dist.all_gather(out, pad)
+            return torch.cat([o[:int(k.item())] for o, k in zip(out, ns)])
+        v, t, ix, c = gather(v), gather(t), gather(ix), gather(c)
+    # dataset order, first of each repeated index; the texts follow their videos
+    order = torch.argsort(ix, stable=True)
+    keep = torch.ones_like(ix, dtype=torch.bool)
+    keep[1:] = ix[order][1:] != ix[order][:-1]
+    order = order[keep]
+    start = torch.cumsum(c, 0) - c
+    rows = torch.cat([torch.arange(int(start[i]), int(start[i] + c[i]), device=dev) for i in order.tolist()])
+    res = dict(video_embd=v[order], text_embd=t[rows], counts=c[order], index=ix[order])
+    return res if not to_host else {k: x.cpu().numpy() for k, x in res.items()}
+
+
+RETRIEVAL_METRICS = ('recall_for_video_text_retrieval', 'video_qa_mc', 'recall_for_video_text_retrieval_varied')
+
+
+def evaluate_retrieval(results, metrics=('recall_for_video_text_retrieval',), topk=0, with_pred=False, v2t=False):
+    """The embedding-similarity branches of ``VideoDataset.evaluate`` (mmaction/datasets/video_dataset.py:173-182
+    ``video_qa_mc``, needs ``results['label']``; :189-195 ``recall_for_video_text_retrieval``; :196-203
+    ``recall_for_video_text_retrieval_varied``, needs ``results['counts']``).  Results that hold device tensors (the
+    test loops with ``to_host=False``) are scored on the device (``recall_on_device``, which is also what ``topk``
+    needs; ``mc_acc_on_device``, which is what ``with_pred`` — the chosen candidate per video as ``'pred'`` — needs;
+    ``recall_varied_on_device``, which is what ``v2t`` needs); numpy results take the reference's host path."""
     out = {}
     v = results['video_embd']
     on_device = getattr(v, 'is_cuda', False)
-    if topk and not on_device:
-        raise ValueError('topk needs device results (multi_gpu_test_retrieval(to_host=False))')
+    if (topk or with_pred or v2t) and not on_device:
+        raise ValueError('topk, with_pred and v2t need device results (the test loop with to_host=False)')
     for metric in ([metrics] if isinstance(metrics, str) else metrics):
-        if metric != 'recall_for_video_text_retrieval':
+        if metric not in RETRIEVAL_METRICS:
             raise KeyError(f'metric {metric} is not supported')                      # video_dataset.py:163-165
+        if metric == 'video_qa_mc':
+            if on_device:
+                out.update(mc_acc_on_device(v, results['text_embd'], results['label'], return_pred=with_pred))
+            else:
+                out.update(acc_for_msrvtt_mc(np.stack(list(v)), np.stack(list(results['text_embd'])),
+                                             results['label'], use_sim=True))
+            continue
+        if metric == 'recall_for_video_text_retrieval_varied':
+            if on_device:
+                out.update(recall_varied_on_device(v, results['text_embd'], results['counts'], v2t=v2t))
+            else:
+                out.update(recall_for_video_text_retrieval_varied(np.stack(list(v)), results['text_embd'],
+                                                                  results['counts']))
+            continue
         if on_device:
             out.update(recall_on_device(v, results['text_embd'], topk=topk))
             continue

@@ -2700,3 +2700,42 @@ def retrieval_rank(query, gallery, gt=None, topk=0):
     check(L.clv_retrieval_rank(_ptr(q), _ptr(g), _ptr(gt), _ptr(rank), _ptr(gscore), _ptr(tidx), _ptr(tscore), _ptr(work),
                                Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), topk, _stream()), 'clv_retrieval_rank')
     return rank, gscore, tidx, tscore
+
+
+def retrieval_group_best(query, gallery, lo=None, hi=None, want_rank=False, eps=0.0):
+    """The best gallery row inside a per-query range (clv_retrieval_group_best; accuracy.py:396-427 without the score
+    matrix).  query fp32 [Nq, D], gallery fp32 [Ng, D] (rows are scaled by 1 / max(norm, eps) inside; eps = 0: all-zero
+    rows stay zero, as retrieval_rank), lo / hi int [Nq]: query i looks at gallery rows [lo[i], hi[i]) (both None: at the
+    whole gallery) ->
+    (best_idx int32 [Nq]: the first row of the range with the highest score, -1 where the range is empty or leaves the
+    gallery;  best_score fp32 [Nq] (NaN there);  rank int32 [Nq] with want_rank, else None: the 0-based position of
+    best_idx in the stable descending order of the query's scores over the WHOLE gallery).  Inference only: no autograd."""
+    _need_gpu(query, gallery, lo, hi)
+    if query.dtype != torch.float32 or gallery.dtype != torch.float32:
+        raise TypeError(f'retrieval_group_best takes fp32 embeddings (got {query.dtype}, {gallery.dtype})')
+    if query.dim() != 2 or gallery.dim() != 2 or query.shape[1] != gallery.shape[1]:
+        raise ValueError(f'retrieval_group_best: query [Nq, D] and gallery [Ng, D] (got {tuple(query.shape)}, '
+                         f'{tuple(gallery.shape)})')
+    if (lo is None) != (hi is None):
+        raise ValueError('retrieval_group_best: lo and hi come together')
+    q, g = query.detach(), gallery.detach()
+    q = q if q.stride(1) == 1 or q.shape[1] == 1 else q.contiguous()
+    g = g if g.stride(1) == 1 or g.shape[1] == 1 else g.contiguous()
+    Nq, D = q.shape
+    Ng = g.shape[0]
+    if lo is not None:
+        if lo.shape != (Nq,) or hi.shape != (Nq,):
+            raise ValueError(f'retrieval_group_best: lo and hi must be [{Nq}] (got {tuple(lo.shape)}, {tuple(hi.shape)})')
+        lo, hi = _c(lo.detach().to(torch.int32)), _c(hi.detach().to(torch.int32))
+    L = _lib.lib()
+    nbytes = L.clv_retrieval_group_work_bytes(Nq, Ng, D)
+    check(min(nbytes, 0), 'clv_retrieval_group_work_bytes')
+    dev = q.device
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    bidx = torch.empty(Nq, device=dev, dtype=torch.int32)
+    bscore = torch.empty(Nq, device=dev, dtype=torch.float32)
+    rank = torch.empty(Nq, device=dev, dtype=torch.int32) if want_rank else None
+    check(L.clv_retrieval_group_best(_ptr(q), _ptr(g), _ptr(lo), _ptr(hi), _ptr(bidx), _ptr(bscore), _ptr(rank), _ptr(work),
+                                     Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), float(eps), _stream()),
+          'clv_retrieval_group_best')
+    return bidx, bscore, rank

@@ -200,7 +200,9 @@ class EvalHook(Hook):
     ``by_epoch=False``) run the test loop over ``dataloader``, compute the metrics, log them and keep the best checkpoint.
 
     ``test_fn``: ``'recall_for_video_text_retrieval'`` or None -> ``multi_gpu_test_retrieval`` + ``evaluate_retrieval``
-    (embeddings stay on the device, ranks from ``ops.retrieval_rank``); ``'use_itm_head_fn'`` ->
+    (embeddings stay on the device, ranks from ``ops.retrieval_rank``; with ``'video_qa_mc'`` among ``metrics`` the loop
+    also collects the labels — zero-shot multiple choice, ``ops.retrieval_group_best`` —, with
+    ``'recall_for_video_text_retrieval_varied'`` it is ``multi_gpu_test_retrieval_varied``); ``'use_itm_head_fn'`` ->
     ``multi_gpu_test_itm_finetune`` + ``evaluate_qa``; a callable ``test_fn(model, dataloader)`` returns the metrics dict
     itself.  EVERY rank runs the test loop (its collection is a collective); rank 0 alone evaluates, appends
     ``dict(epoch, **metrics)`` to ``records``, prints it through ``printer`` (what ``LogHook`` is given) and saves.
@@ -332,7 +334,7 @@ class EvalHook(Hook):
 
     def _test(self, model):
         from .evaluation import (evaluate_qa, evaluate_retrieval, multi_gpu_test_itm_finetune,
-                                 multi_gpu_test_retrieval)
+                                 multi_gpu_test_retrieval, multi_gpu_test_retrieval_varied)
         rank, _ = self._rank_world()
         if callable(self.test_fn):
             res = self.test_fn(model, self.dataloader)
@@ -340,7 +342,11 @@ class EvalHook(Hook):
         if self.test_fn == 'use_itm_head_fn':
             res = multi_gpu_test_itm_finetune(model, self.dataloader)
             return evaluate_qa(res, self.metrics) if rank == 0 else None
-        res = multi_gpu_test_retrieval(model, self.dataloader, gpu_collect=self.gpu_collect, to_host=False)
+        if 'recall_for_video_text_retrieval_varied' in self.metrics:
+            res = multi_gpu_test_retrieval_varied(model, self.dataloader, to_host=False)
+        else:
+            res = multi_gpu_test_retrieval(model, self.dataloader, gpu_collect=self.gpu_collect, to_host=False,
+                                           with_label='video_qa_mc' in self.metrics)
         return evaluate_retrieval(res, self.metrics) if rank == 0 else None
 
     def _do_evaluate(self, runner):

@@ -671,6 +671,28 @@ int clv_retrieval_rank(const float* query, const float* gallery, const int32_t* 
                        int32_t* topk_idx, float* topk_score, void* work, int64_t Nq, int64_t Ng, int32_t D, int64_t ldq,
                        int64_t ldg, int32_t topk, void* stream);
 
+/* The best gallery row inside a per-query range, and its rank (zero-shot multiple choice: acc_for_msrvtt_mc,
+ * mmaction/core/evaluation/accuracy.py:396-427, without the [N][C N] matrix whose block diagonal it keeps; the video -> text
+ * direction of a test set whose videos have several captions each).  query / gallery as clv_retrieval_rank, rows scaled by
+ * 1 / max(norm, eps) (sim_matrix, accuracy.py:385-394, passes 1e-8; eps = 0 is clv_retrieval_rank's normalisation: an
+ * all-zero row stays zero), s[i][j] by the tile loop of clv_retrieval_rank: bit-equal to the scores it compares.
+ * lo, hi int32 [Nq]: query i looks at the gallery rows [lo[i], hi[i]); both NULL: at the whole gallery.
+ *   best_idx[i]   = the FIRST j in [lo[i], hi[i]) that attains max s[i][j] over that range (torch.argmax's tie rule);
+ *                   -1 where the range is empty or leaves [0, Ng]
+ *   best_score[i] = that maximum (NaN where best_idx[i] = -1)
+ *   rank[i]       (may be NULL: not computed) = clv_retrieval_rank's rank with gt = best_idx: the 0-based position of
+ *                   best_idx[i] in the stable descending order of the WHOLE row i; -1 where best_idx[i] = -1.  With the
+ *                   range = the captions of video i this is the usual video -> text rank: no other caption of the set
+ *                   scores higher than the best one or ties in front of it.
+ * A workgroup (64 queries) walks only the gallery tiles that meet [min lo, max hi) of its queries.
+ * work: clv_retrieval_group_work_bytes(...) bytes, 16-byte aligned; nothing is allocated inside, every launch goes to
+ * `stream` (capturable).  Shape limits and error codes of clv_retrieval_rank.  Results are deterministic: the chunks of a
+ * long gallery meet in a merge ordered by (score descending, index ascending), ranks through int32 adds. */
+int64_t clv_retrieval_group_work_bytes(int64_t Nq, int64_t Ng, int32_t D);
+int clv_retrieval_group_best(const float* query, const float* gallery, const int32_t* lo, const int32_t* hi,
+                             int32_t* best_idx, float* best_score, int32_t* rank, void* work, int64_t Nq, int64_t Ng,
+                             int32_t D, int64_t ldq, int64_t ldg, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

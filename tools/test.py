@@ -10,6 +10,12 @@ rank-major; embeddings are collected over RCCL and rank 0 computes R@1/5/10, med
 scope: ``data.synthetic_test`` describes a synthetic test set (``pairs`` random (clip, caption) pairs, so the metrics
 of an untrained model sit at chance: R@K ~ 100 K / pairs).
 
+Zero-shot multiple choice (``evaluation = dict(metrics=['video_qa_mc'], test_fn='recall_for_video_text_retrieval')``, the
+reference's finetune_msrvtt_mc.py; ``synthetic_test.candidates = C`` captions per video) and the many-caption protocol
+(``recall_for_video_text_retrieval_varied`` in the config or after ``--eval``; ``synthetic_test.captions`` = counts per
+video, ``--v2t`` adds the video -> text keys) run the same two encoders; their scores stay on the device
+(ops.retrieval_group_best) and ``--out`` holds the chosen candidate per video as ``pred``.
+
 Video QA / fill-in-the-blank (a config with ``evaluation.test_fn='use_itm_head_fn'``, or ``--eval video_qa_mc`` /
 ``video_qa_oe``): ``forward_test`` scores every sample (multi_gpu_test_itm_finetune, my_eval_hook.py:317-380) and rank 0
 prints ``acc`` / ``overall_acc`` (video_dataset.py:304-343) over ``data.synthetic_test`` = dict(pairs, frames, tokens,
@@ -36,6 +42,8 @@ def parse_args():
     p.add_argument('--gpu-collect', action='store_true', help='accepted for CLI compatibility (collection is always RCCL)')
     p.add_argument('--topk', type=int, default=0,
                    help='retrieval only: score on the device and add the K best video indices per query to --out (1..16)')
+    p.add_argument('--v2t', action='store_true',
+                   help='recall_for_video_text_retrieval_varied only: add V2T_Recall@K / V2T_MR (best caption per video)')
     p.add_argument('--cfg-options', nargs='+', default=[], help='a.b=c overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher')
     return p.parse_args()
@@ -46,12 +54,18 @@ from clover_amd.utils.synthetic_loaders import SyntheticTestLoader      # noqa: 
 
 def select_test(cfg, eval_metrics):
     """-> ('qa' | 'retrieval', metrics): the video-QA test loop when the config asks for it (evaluation.test_fn ==
-    'use_itm_head_fn', as the reference's tools/test.py) or the metrics are video-QA ones; retrieval otherwise."""
-    from clover_amd.evaluation import QA_METRICS
+    'use_itm_head_fn', as the reference's tools/test.py) or the --eval metrics are video-QA ones; retrieval otherwise,
+    with the config's evaluation.metrics when --eval names none.  A config whose evaluation.test_fn is
+    'recall_for_video_text_retrieval' (the reference's finetune_msrvtt_mc.py) keeps the embedding test loop whatever
+    the metric: 'video_qa_mc' is then answered zero-shot from the retrieval embeddings."""
+    from clover_amd.evaluation import QA_METRICS, RETRIEVAL_METRICS
     ev = cfg.get('evaluation') or {}
-    qa = ev.get('test_fn') == 'use_itm_head_fn' or any(m in QA_METRICS for m in (eval_metrics or []))
+    cfg_metrics = [ev.get('metrics')] if isinstance(ev.get('metrics'), str) else list(ev.get('metrics') or [])
+    embed = ev.get('test_fn') == 'recall_for_video_text_retrieval'
+    qa = not embed and (ev.get('test_fn') == 'use_itm_head_fn' or any(m in QA_METRICS for m in (eval_metrics or [])))
     if not qa:
-        return 'retrieval', eval_metrics or ['recall_for_video_text_retrieval']
+        metrics = eval_metrics or [m for m in cfg_metrics if m in RETRIEVAL_METRICS]
+        return 'retrieval', metrics or ['recall_for_video_text_retrieval']
     metrics = eval_metrics or list(ev.get('metrics', ['video_qa_mc']))
     bad = [m for m in metrics if m not in QA_METRICS]
     if bad:
@@ -63,13 +77,17 @@ def main():
     args = parse_args()
     from clover_amd.runner import Config, parse_cfg_options
     from clover_amd.evaluation import (evaluate_qa, evaluate_retrieval, multi_gpu_test_itm_finetune,
-                                       multi_gpu_test_retrieval)
+                                       multi_gpu_test_retrieval, multi_gpu_test_retrieval_varied)
     import clover_amd
     cfg = Config.fromfile(args.config)
     cfg.merge_from_dict(parse_cfg_options(args.cfg_options))
     kind, metrics = select_test(cfg, args.eval)
     if args.topk and (kind != 'retrieval' or not 1 <= args.topk <= 16):
         raise SystemExit('--topk K: the retrieval test only, K in 1..16')
+    mc = kind == 'retrieval' and 'video_qa_mc' in metrics
+    varied = kind == 'retrieval' and 'recall_for_video_text_retrieval_varied' in metrics
+    if args.v2t and not varied:
+        raise SystemExit('--v2t: with recall_for_video_text_retrieval_varied only')
     if not torch.cuda.is_available():
         raise SystemExit('tools/test.py needs an MI355X (no CPU fallback)')
     if args.launcher == 'none':
@@ -95,23 +113,30 @@ def main():
     model.eval()
     st = cfg.data.get('synthetic_test', dict(pairs=64, frames=8, tokens=32))
     loader = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
-                                 st.get('tokens', 32), rank, world, dev, qa=st.get('qa') if kind == 'qa' else None)
+                                 st.get('tokens', 32), rank, world, dev, qa=st.get('qa') if kind == 'qa' else None,
+                                 candidates=st.get('candidates') if mc else None,
+                                 captions=st.get('captions') if varied else None)
+    on_device = bool(args.topk) or mc or varied           # scored on the device: only small integer vectors come back
     if kind == 'qa':
         results = multi_gpu_test_itm_finetune(model, loader)
+    elif varied:
+        results = multi_gpu_test_retrieval_varied(model, loader, to_host=False)
     else:
-        results = multi_gpu_test_retrieval(model, loader, to_host=not args.topk)
+        results = multi_gpu_test_retrieval(model, loader, to_host=not on_device, with_label=mc)
     if rank == 0:
-        if args.topk:                                     # ranks and the K best videos per query from the device
-            metrics = evaluate_retrieval(results, metrics, topk=args.topk)
+        if on_device:                                     # ranks, the K best videos per query, the chosen candidates
+            metrics = evaluate_retrieval(results, metrics, topk=args.topk, with_pred=mc, v2t=args.v2t)
         else:
             metrics = (evaluate_qa if kind == 'qa' else evaluate_retrieval)(results, metrics)
-        topk = metrics.pop('topk', None)
+        topk, pred = metrics.pop('topk', None), metrics.pop('pred', None)
         for k, v in metrics.items():
             print(f'{k}: {v:.04f}')                                                   # tools/test.py:255-256
         if args.out:
             out = dict(metrics={k: float(v) for k, v in metrics.items()}, pairs=int(len(results['index'])))
             if topk is not None:
                 out['topk'] = topk.tolist()
+            if pred is not None:
+                out['pred'] = pred.tolist()
             with open(args.out, 'w') as f:
                 json.dump(out, f)
     if dist.is_initialized():

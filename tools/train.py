@@ -118,8 +118,14 @@ def main():
         ev = dict(cfg.get('evaluation') or {})
         st = cfg.data.get('synthetic_test', dict(pairs=64, frames=8, tokens=32))
         qa = st.get('qa') if ev.get('test_fn') == 'use_itm_head_fn' else None
+        embed = ev.get('test_fn') in (None, 'recall_for_video_text_retrieval')       # routed by the metrics, as EvalHook
+        ev_metrics = [ev.get('metrics')] if isinstance(ev.get('metrics'), str) else list(ev.get('metrics') or [])
+        mc = embed and 'video_qa_mc' in ev_metrics
+        varied = embed and 'recall_for_video_text_retrieval_varied' in ev_metrics
         val = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
-                                  st.get('tokens', 32), rank, world, dev, qa=qa)
+                                  st.get('tokens', 32), rank, world, dev, qa=qa,
+                                  candidates=st.get('candidates') if mc else None,
+                                  captions=st.get('captions') if varied else None)
         runner.register_hook(EvalHook(val, printer=print if rank == 0 else None, **ev))
     if args.resume_from:
         runner.resume(args.resume_from)
