@@ -144,6 +144,13 @@ SIGNATURES = {
     'clv_normsoftmax_work_floats': (C.c_int64, [_i32, _i32]),
     'clv_normsoftmax_fwd': (C.c_int, [_p] * 5 + [_i32, _i32, _f, _f, _p]),
     'clv_normsoftmax_bwd': (C.c_int, [_p] * 6 + [_i32, _i32, _f, _p]),
+    'clv_infonce_large_min_g': (C.c_int32, []),
+    'clv_infonce_fwd_large': (C.c_int, [_p] * 6 + [_i32, _i32, _i32, _f, _f, _p]),
+    'clv_infonce_bwd_large': (C.c_int, [_p] * 10 + [_i32, _i32, _i32, _f, _f, _p]),
+    'clv_infonce_pair_fwd_large': (C.c_int, [_p] * 4 + [_i32, _i32, _i32, _f, _f, _p]),
+    'clv_infonce_pair_bwd_large': (C.c_int, [_p] * 4 + [_i32, _i32, _i32, _f, _f, _p]),
+    'clv_normsoftmax_fwd_large': (C.c_int, [_p] * 5 + [_i32, _i32, _f, _f, _p]),
+    'clv_normsoftmax_bwd_large': (C.c_int, [_p] * 6 + [_i32, _i32, _f, _p]),
     'clv_sumsq': (C.c_int, [_p, _p, _i64, _p]),
     'clv_adamw_step': (C.c_int, [_p] * 6 + [_i64] + [_f] * 9 + [_p]),
     'clv_gemm_nt_supported': (C.c_int, [_i64, _i32, _i32]),

@@ -176,12 +176,13 @@ __global__ void __launch_bounds__(FC_WIDE) focal_bwd_pairs_kernel(
 //   dsim [G][3][G]    d loss / d sim, row-major in (i, k, j)
 //   dsimT[3][G][G]    transposed per block: [k][j][i]
 //   den  [4][G][Dm]   d loss / d normalised embeddings
-//   acc  [2]
+//   acc  [16]
+//   term [6][G]       multi-workgroup path only: diag - lse of every exclusive row, then of every column
 struct NceWork {
-    float *en, *enT, *invn, *sim, *lser, *lsec, *dsim, *dsimT, *den, *acc;
+    float *en, *enT, *invn, *sim, *lser, *lsec, *dsim, *dsimT, *den, *acc, *term;
 };
 __host__ __device__ inline int64_t nce_work_floats(int G, int Dm) {
-    return (int64_t)4 * G * Dm * 3 + (int64_t)4 * G + (int64_t)3 * G * G * 3 + (int64_t)6 * G + 16;
+    return (int64_t)4 * G * Dm * 3 + (int64_t)4 * G + (int64_t)3 * G * G * 3 + (int64_t)6 * G + 16 + (int64_t)6 * G;
 }
 __host__ __device__ inline NceWork nce_carve(float* w, int G, int Dm) {
     NceWork W;
@@ -194,7 +195,8 @@ __host__ __device__ inline NceWork nce_carve(float* w, int G, int Dm) {
     W.dsimT = w; w += (int64_t)3 * G * G;
     W.lser = w; w += 3 * G;
     W.lsec = w; w += 3 * G;
-    W.acc = w;
+    W.acc = w; w += 16;
+    W.term = w;
     return W;
 }
 
@@ -449,12 +451,12 @@ __global__ void __launch_bounds__(256) nce_pair_norm_bwd_kernel(NcePair P, float
 // loss = -mean_i diag(log_softmax(x, 1)) - mean_j diag(log_softmax(x^T, 1)).
 // work layout (floats):
 //   en [2][G][Dm], enT [Dm][2][G], den [2][G][Dm], invn [2][G], sim [G][G], dsim [G][G], dsimT [G][G],
-//   lser [G], lsec [G]
+//   lser [G], lsec [G], 16 spare, term [2][G] (multi-workgroup path only: diag - lse of every row, then of every column)
 struct NsWork {
-    float *en, *enT, *den, *invn, *sim, *dsim, *dsimT, *lser, *lsec;
+    float *en, *enT, *den, *invn, *sim, *dsim, *dsimT, *lser, *lsec, *term;
 };
 __host__ __device__ inline int64_t ns_work_floats(int G, int Dm) {
-    return (int64_t)2 * G * Dm * 3 + (int64_t)2 * G + (int64_t)G * G * 3 + (int64_t)2 * G + 16;
+    return (int64_t)2 * G * Dm * 3 + (int64_t)2 * G + (int64_t)G * G * 3 + (int64_t)2 * G + 16 + (int64_t)2 * G;
 }
 __host__ __device__ inline NsWork ns_carve(float* w, int G, int Dm) {
     NsWork W;
@@ -466,7 +468,8 @@ __host__ __device__ inline NsWork ns_carve(float* w, int G, int Dm) {
     W.dsim = w; w += (int64_t)G * G;
     W.dsimT = w; w += (int64_t)G * G;
     W.lser = w; w += G;
-    W.lsec = w;
+    W.lsec = w; w += G + 16;
+    W.term = w;
     return W;
 }
 
@@ -539,6 +542,206 @@ __global__ void __launch_bounds__(256) ns_norm_bwd_kernel(NsWork W, float* d0, f
     const float inv = W.invn[row];
     const bool clamped = inv < 0.f;
     for (int c = lane; c < Dm; c += 64) d[c] = clamped ? de[c] * -inv : inv * (de[c] - en[c] * s);
+}
+
+// =========================================================================== the loss section at a global batch
+// The one-workgroup kernels above serve a device batch (G <= ~100).  With virtual ranks G is the GLOBAL batch (1024 at the
+// reference's headline configuration): 6 G log-sum-exps over G or 3 G scores each, 19 M exponentials on one CU.  The kernels
+// below spread them over the device and keep the result reproducible — no float atomics, every sum in a fixed order:
+//   lse_rows_kernel : one wave per exclusive row; its NB rows of G scores are contiguous, lanes stride them; ONE pass with a
+//                     running (max, sum) per lane (as focal_fwd_pairs_kernel), merged across the wave
+//   lse_cols_kernel : 64 adjacent columns per workgroup (a lane = a column: every global read is contiguous across the
+//                     wave), 16 waves share the G rows; the 16 (max, sum) pairs of a column meet in LDS in wave order
+//   *_finish_kernel : one workgroup sums the per-row terms diag - lse in a fixed order and writes the losses
+// lser / lsec are written exactly as the one-workgroup kernels write them: the backward kernels are shared.
+constexpr int LSE_COL_WAVES = 16;
+
+__device__ __forceinline__ void lse_push(float& m, float& s, float x) {
+    const float mn = fmaxf(m, x);
+    if (mn == -INFINITY) return;
+    s = s * __expf(m - mn) + __expf(x - mn);                  // first value: 0 * exp(-inf) = 0
+    m = mn;
+}
+
+template <int NB>
+__device__ __forceinline__ void lse_rows_body(const float* __restrict__ sim, float* __restrict__ lser,
+                                              float* __restrict__ term, int G) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= NB * G) return;
+    const int kx = t / G, i = t - kx * G;
+    float m = -INFINITY, s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+        const float* row = sim + ((int64_t)k * G + i) * G;
+        for (int j = lane; j < G; j += 64) {
+            float x = row[j];
+            if (k != kx && j == i) x = x - (x + 10000.f);     // nce_entry: the other blocks' diagonals
+            lse_push(m, s, x);
+        }
+    }
+    const float wm = wave_max(m);
+    s = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - wm));  // a lane without elements (G < 64)
+    if (lane == 0) {
+        const float lse = wm + __logf(s);
+        lser[t] = lse;
+        term[t] = sim[((int64_t)kx * G + i) * G + i] - lse;
+    }
+}
+
+__device__ __forceinline__ void lse_cols_body(const float* __restrict__ sim, float* __restrict__ lsec,
+                                              float* __restrict__ term, int G) {
+    __shared__ float shm[LSE_COL_WAVES][64], shs[LSE_COL_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int k = blockIdx.y, j = blockIdx.x * 64 + lane;
+    const float* blk = sim + (int64_t)k * G * G;
+    float m = -INFINITY, s = 0.f;
+    if (j < G)
+        for (int i = wv; i < G; i += LSE_COL_WAVES) lse_push(m, s, blk[(int64_t)i * G + j]);
+    shm[wv][lane] = m;
+    shs[wv][lane] = s;
+    __syncthreads();
+    if (wv != 0 || j >= G) return;
+    float bm = shm[0][lane];
+#pragma unroll
+    for (int w = 1; w < LSE_COL_WAVES; ++w) bm = fmaxf(bm, shm[w][lane]);
+    float bs = 0.f;
+#pragma unroll
+    for (int w = 0; w < LSE_COL_WAVES; ++w)
+        if (shm[w][lane] != -INFINITY) bs += shs[w][lane] * __expf(shm[w][lane] - bm);
+    const float lse = bm + __logf(bs);
+    lsec[k * G + j] = lse;
+    term[k * G + j] = blk[(int64_t)j * G + j] - lse;
+}
+
+__device__ __forceinline__ void nce_finish_body(const NceWork& W, float* __restrict__ out, int G, float margin) {
+    __shared__ float sh[16];
+    float part_v = 0.f, part_t = 0.f, part_r = 0.f;
+    for (int t = threadIdx.x; t < 3 * G; t += blockDim.x) {
+        part_v += W.term[t];
+        part_t += W.term[3 * G + t];
+    }
+    for (int i = threadIdx.x; i < G; i += blockDim.x) {
+        const float a = W.sim[((int64_t)0 * G + i) * G + i], b = W.sim[((int64_t)1 * G + i) * G + i];
+        part_r += fmaxf(0.f, -(a - b) + margin);
+    }
+    const float sv = block_reduce(part_v, sh, false);
+    const float stt = block_reduce(part_t, sh, false);
+    const float sr = block_reduce(part_r, sh, false);
+    if (threadIdx.x == 0) {
+        out[0] = -(sv / (float)G) + -(stt / (float)(3 * G));
+        out[1] = sr / (float)G;
+    }
+}
+
+__global__ void __launch_bounds__(256) nce_lse_rows_kernel(NceWork W, int G) {
+    lse_rows_body<3>(W.sim, W.lser, W.term, G);
+}
+__global__ void __launch_bounds__(256) nce_pair_lse_rows_kernel(NcePair P, int G) {
+    const NceWork& W = P.w[blockIdx.y];
+    lse_rows_body<3>(W.sim, W.lser, W.term, G);
+}
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) nce_lse_cols_kernel(NceWork W, int G) {
+    lse_cols_body(W.sim, W.lsec, W.term + 3 * G, G);
+}
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) nce_pair_lse_cols_kernel(NcePair P, int G) {
+    const NceWork& W = P.w[blockIdx.z];
+    lse_cols_body(W.sim, W.lsec, W.term + 3 * G, G);
+}
+__global__ void __launch_bounds__(256) nce_finish_kernel(NceWork W, float* __restrict__ out, int G, float margin) {
+    nce_finish_body(W, out, G, margin);
+}
+__global__ void __launch_bounds__(256) nce_pair_finish_kernel(NcePair P, float* __restrict__ out, int G, float margin) {
+    nce_finish_body(P.w[blockIdx.x], out + 2 * blockIdx.x, G, margin);
+}
+__global__ void __launch_bounds__(256) ns_lse_rows_kernel(NsWork W, const float* __restrict__ sim, int G) {
+    lse_rows_body<1>(sim, W.lser, W.term, G);
+}
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) ns_lse_cols_kernel(NsWork W, const float* __restrict__ sim, int G) {
+    lse_cols_body(sim, W.lsec, W.term + G, G);
+}
+__global__ void __launch_bounds__(256) ns_finish_kernel(NsWork W, float* __restrict__ out, int G) {
+    __shared__ float sh[16];
+    float part = 0.f;
+    for (int t = threadIdx.x; t < 2 * G; t += blockDim.x) part += W.term[t];
+    const float tot = block_reduce(part, sh, false);
+    if (threadIdx.x == 0) out[0] = -(tot / (float)G);
+}
+
+// C[i][j] (ldc) = alpha * sum_k A[i][k] * B[j][k], batched like sgemm_nt_kernel, as 64 x 64 x 16 LDS tiles (4 waves, 32 x 32
+// each, exact-f32 MFMA 16x16x4; the tile loop of parity.hip's sgemm_tiled_kernel).  sgemm_nt_kernel gives every 16 x 16 tile
+// a wave of its own, which re-reads each operand row from L2 once per tile across: G / 16 = 64 times at G = 1024.
+constexpr int LT_BM = 64, LT_BN = 64, LT_BK = 16, LT_LD = LT_BK + 1;
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) sgemm_nt_tiled_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                             float* __restrict__ C, int M, int N, int K, int lda, int ldb,
+                                                             int ldc, int64_t sA, int64_t sB, int64_t sC, float alpha,
+                                                             int zb, int64_t s2) {
+    __shared__ float As[LT_BM * LT_LD], Bs[LT_BN * LT_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lg = lane >> 4, lr = lane & 15;
+    const int z1 = blockIdx.z / zb, z0 = blockIdx.z - z1 * zb;
+    A += sA * z0 + s2 * z1;
+    B += sB * z0 + s2 * z1;
+    C += sC * z0 + s2 * z1;
+    const int m0 = blockIdx.y * LT_BM, n0 = blockIdx.x * LT_BN;
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+    f32x4_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    const int srow = tid >> 2, sk = (tid & 3) * 4;            // staging: four floats of A and of B per thread
+    const int am = m0 + srow, bn = n0 + srow;
+    for (int k0 = 0; k0 < K; k0 += LT_BK) {
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+        if (VEC) {
+            if (am < M) av = *reinterpret_cast<const float4*>(A + (int64_t)am * lda + k0 + sk);
+            if (bn < N) bv = *reinterpret_cast<const float4*>(B + (int64_t)bn * ldb + k0 + sk);
+        } else {
+            float* a4 = reinterpret_cast<float*>(&av);
+            float* b4 = reinterpret_cast<float*>(&bv);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int kk = k0 + sk + e;
+                if (am < M && kk < K) a4[e] = A[(int64_t)am * lda + kk];
+                if (bn < N && kk < K) b4[e] = B[(int64_t)bn * ldb + kk];
+            }
+        }
+        __syncthreads();                                      // the previous step's fragment reads are done
+        float* as = As + srow * LT_LD + sk;
+        float* bs = Bs + srow * LT_LD + sk;
+        as[0] = av.x; as[1] = av.y; as[2] = av.z; as[3] = av.w;
+        bs[0] = bv.x; bs[1] = bv.y; bs[2] = bv.z; bs[3] = bv.w;
+        __syncthreads();
+#pragma unroll
+        for (int k4 = 0; k4 < LT_BK; k4 += 4) {
+            float a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                a[i] = As[(wr + i * 16 + lr) * LT_LD + k4 + lg];
+                b[i] = Bs[(wc + i * 16 + lr) * LT_LD + k4 + lg];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+    }
+    // acc[i][j][r] = C[m0 + wr + i*16 + lg*4 + r][n0 + wc + j*16 + lr]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int cn = n0 + wc + j * 16 + lr;
+            if (cn >= N) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int cm = m0 + wr + i * 16 + lg * 4 + r;
+                if (cm < M) C[(int64_t)cm * ldc + cn] = alpha * acc[i][j][r];
+            }
+        }
 }
 
 }  // namespace
@@ -618,9 +821,29 @@ static int nce_loss_threads(int G) {
     return t < 64 ? 64 : (t > 1024 ? 1024 : t);
 }
 
+// The loss section at and above this many rows takes the multi-workgroup path (log-sum-exp kernels over the device, LDS-tiled
+// GEMMs); below it the one-workgroup kernels, unchanged.  Measured (tools/virtual_ranks_bench.py, DESIGN section 5: forward +
+// backward of the pair form, Dm = 768, old / new): as one hipGraph replay 0.89 x at G = 16, 1.02 x at 32, 1.17 x at 64,
+// 1.83 x at 128, 4.2 x at 256, 19 x at 1024; issued eagerly, as the engine's loss section issues it (the new forward is five
+// launches where the old one is three), 0.98 x at 32, 0.96 x at 64, 1.25 x at 128, 3.3 x at 256, 19 x at 1024.  The crossover
+// of the eager form lies between 64 and 128: the threshold is the smallest size measured at which both forms are ahead.
+constexpr int NCE_LARGE_MIN_G = 128;
+
 static int nce_gemm(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                     int batch, int64_t sA, int64_t sB, int64_t sC, float alpha, hipStream_t st, int outer = 1,
-                    int64_t s2 = 0) {
+                    int64_t s2 = 0, bool tiled = false) {
+    if (tiled) {
+        const dim3 tgrid((N + LT_BN - 1) / LT_BN, (M + LT_BM - 1) / LT_BM, batch * outer);
+        const bool vec = K % LT_BK == 0 && lda % 4 == 0 && ldb % 4 == 0 && sA % 4 == 0 && sB % 4 == 0 && s2 % 4 == 0 &&
+                         reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0;
+        if (vec)
+            hipLaunchKernelGGL(sgemm_nt_tiled_kernel<true>, tgrid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
+                               sC, alpha, batch, s2);
+        else
+            hipLaunchKernelGGL(sgemm_nt_tiled_kernel<false>, tgrid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
+                               sC, alpha, batch, s2);
+        return clv_check_launch();
+    }
     const dim3 grid((N + 15) / 16, (M + 15) / 16, batch * outer);
     if (K >= 256 && (int64_t)grid.x * grid.y * batch <= 512)       // few tiles (per evaluation), long contraction: 8 waves share a tile
         hipLaunchKernelGGL(sgemm_nt_kernel<8>, grid, dim3(512), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, alpha,
@@ -631,9 +854,9 @@ static int nce_gemm(const float* A, const float* B, float* C, int M, int N, int 
     return clv_check_launch();
 }
 
-extern "C" int clv_infonce_fwd(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
-                               float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
-                               void* stream) {
+static int infonce_fwd_impl(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
+                            float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
+                            void* stream, bool large) {
     if (!e0 || !e1 || !e2 || !e3 || !out || !work || G <= 0 || Dm <= 0 || ld < Dm || temperature <= 0.f)
         return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -644,15 +867,35 @@ extern "C" int clv_infonce_fwd(const float* e0, const float* e1, const float* e2
     if (rc) return rc;
     // sim[k] = en0 . en_{k+1}^T / temperature
     rc = nce_gemm(W.en, W.en + (int64_t)G * Dm, W.sim, G, G, Dm, Dm, Dm, G, 3, 0, (int64_t)G * Dm, (int64_t)G * G,
-                  1.0f / temperature, st);
+                  1.0f / temperature, st, 1, 0, large);
     if (rc) return rc;
-    hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(nce_loss_threads(G)), 0, st, W, out, (int)G, margin);
+    if (!large) {
+        hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(nce_loss_threads(G)), 0, st, W, out, (int)G, margin);
+        return clv_check_launch();
+    }
+    hipLaunchKernelGGL(nce_lse_rows_kernel, dim3((3 * G + 3) / 4), dim3(256), 0, st, W, (int)G);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(nce_lse_cols_kernel, dim3((G + 63) / 64, 3), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(nce_finish_kernel, dim3(1), dim3(256), 0, st, W, out, (int)G, margin);
     return clv_check_launch();
 }
 
-extern "C" int clv_infonce_bwd(const float* e0, const float* e1, const float* e2, const float* e3, const float* dout,
-                               const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G, int32_t Dm,
-                               int32_t ldd, float temperature, float margin, void* stream) {
+extern "C" int32_t clv_infonce_large_min_g(void) { return NCE_LARGE_MIN_G; }
+
+extern "C" int clv_infonce_fwd(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
+                               float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
+                               void* stream) {
+    return infonce_fwd_impl(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, false);
+}
+extern "C" int clv_infonce_fwd_large(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
+                                     float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
+                                     void* stream) {
+    return infonce_fwd_impl(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, true);
+}
+
+static int infonce_bwd_impl(const float* dout, const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G,
+                            int32_t Dm, int32_t ldd, float temperature, float margin, void* stream, bool large) {
     if (!dout || !work || !d0 || !d1 || !d2 || !d3 || G <= 0 || Dm <= 0 || ldd < Dm) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     NceWork W = nce_carve(const_cast<float*>(work), G, Dm);
@@ -664,15 +907,26 @@ extern "C" int clv_infonce_bwd(const float* e0, const float* e1, const float* e2
     if (rc) return rc;
     const float it = 1.0f / temperature;
     // d en0[i][d] = sum_{k,j} dsim[i][(k,j)] * en_{k+1}[j][d] / T :  A = dsim [G][3G], B = enT[d][(k+1, j)]
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st);
+    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
     if (rc) return rc;
     // d en_{k+1}[j][d] = sum_i dsimT[k][j][i] * en0[i][d] / T   :  A = dsimT[k] [G][G], B = enT[d][(0, i)]
     rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 4 * G, Dm, 3, (int64_t)G * G, 0,
-                  (int64_t)G * Dm, it, st);
+                  (int64_t)G * Dm, it, st, 1, 0, large);
     if (rc) return rc;
     hipLaunchKernelGGL(nce_norm_bwd_kernel, dim3((4 * G + 3) / 4), dim3(256), 0, st, W, d0, d1, d2, d3, (int)G, (int)Dm,
                        (int)ldd);
     return clv_check_launch();
+}
+
+extern "C" int clv_infonce_bwd(const float* e0, const float* e1, const float* e2, const float* e3, const float* dout,
+                               const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G, int32_t Dm,
+                               int32_t ldd, float temperature, float margin, void* stream) {
+    return infonce_bwd_impl(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, false);
+}
+extern "C" int clv_infonce_bwd_large(const float* e0, const float* e1, const float* e2, const float* e3, const float* dout,
+                                     const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G, int32_t Dm,
+                                     int32_t ldd, float temperature, float margin, void* stream) {
+    return infonce_bwd_impl(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, true);
 }
 
 static bool nce_pair_setup(NcePair& P, const float* packed, float* work, const int32_t* slots, int G, int k, int Dm) {
@@ -692,8 +946,8 @@ static bool nce_pair_setup(NcePair& P, const float* packed, float* work, const i
     return true;
 }
 
-extern "C" int clv_infonce_pair_fwd(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
-                                    int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
+static int infonce_pair_fwd_impl(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
+                                 int32_t k, int32_t Dm, float temperature, float margin, void* stream, bool large) {
     if (!packed || !slots || !out || !work || G <= 0 || k < 4 || Dm <= 0 || temperature <= 0.f) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     NcePair P;
@@ -704,14 +958,32 @@ extern "C" int clv_infonce_pair_fwd(const float* packed, const int32_t* slots, f
     int rc = clv_check_launch();
     if (rc) return rc;
     rc = nce_gemm(P.w[0].en, P.w[0].en + (int64_t)G * Dm, P.w[0].sim, G, G, Dm, Dm, Dm, G, 3, 0, (int64_t)G * Dm,
-                  (int64_t)G * G, 1.0f / temperature, st, 2, ws);
+                  (int64_t)G * G, 1.0f / temperature, st, 2, ws, large);
     if (rc) return rc;
-    hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(2), dim3(nce_loss_threads(G)), 0, st, P, out, (int)G, margin);
+    if (!large) {
+        hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(2), dim3(nce_loss_threads(G)), 0, st, P, out, (int)G, margin);
+        return clv_check_launch();
+    }
+    hipLaunchKernelGGL(nce_pair_lse_rows_kernel, dim3((3 * G + 3) / 4, 2), dim3(256), 0, st, P, (int)G);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(nce_pair_lse_cols_kernel, dim3((G + 63) / 64, 3, 2), dim3(64 * LSE_COL_WAVES), 0, st, P, (int)G);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(nce_pair_finish_kernel, dim3(2), dim3(256), 0, st, P, out, (int)G, margin);
     return clv_check_launch();
 }
 
-extern "C" int clv_infonce_pair_bwd(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
-                                    int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
+extern "C" int clv_infonce_pair_fwd(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
+                                    int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
+    return infonce_pair_fwd_impl(packed, slots, out, work, G, k, Dm, temperature, margin, stream, false);
+}
+extern "C" int clv_infonce_pair_fwd_large(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
+                                          int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
+    return infonce_pair_fwd_impl(packed, slots, out, work, G, k, Dm, temperature, margin, stream, true);
+}
+
+static int infonce_pair_bwd_impl(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
+                                 int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream,
+                                 bool large) {
     if (!dout || !work || !slots || !dpacked || G <= 0 || k < 4 || Dm <= 0 || temperature <= 0.f) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     NcePair P;
@@ -726,20 +998,31 @@ extern "C" int clv_infonce_pair_bwd(const float* const* dout, const float* work,
     if (rc) return rc;
     const float it = 1.0f / temperature;
     const NceWork& W = P.w[0];
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st, 2, ws);
+    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st, 2, ws, large);
     if (rc) return rc;
     rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 4 * G, Dm, 3, (int64_t)G * G, 0,
-                  (int64_t)G * Dm, it, st, 2, ws);
+                  (int64_t)G * Dm, it, st, 2, ws, large);
     if (rc) return rc;
     hipLaunchKernelGGL(nce_pair_norm_bwd_kernel, dim3((k * G + 3) / 4), dim3(256), 0, st, P, dpacked, (int)G, (int)k,
                        (int)Dm);
     return clv_check_launch();
 }
 
+extern "C" int clv_infonce_pair_bwd(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
+                                    int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
+    return infonce_pair_bwd_impl(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, false);
+}
+extern "C" int clv_infonce_pair_bwd_large(const float* const* dout, const float* work, const int32_t* slots,
+                                          float* dpacked, int32_t G, int32_t k, int32_t Dm, float temperature, float margin,
+                                          void* stream) {
+    return infonce_pair_bwd_impl(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, true);
+}
+
 extern "C" int64_t clv_normsoftmax_work_floats(int32_t G, int32_t Dm) { return ns_work_floats(G, Dm > 0 ? Dm : 1); }
 
-extern "C" int clv_normsoftmax_fwd(const float* video, const float* text, const float* sim_mat, float* out,
-                                   float* work, int32_t G, int32_t Dm, float temperature, float eps, void* stream) {
+static int normsoftmax_fwd_impl(const float* video, const float* text, const float* sim_mat, float* out,
+                                float* work, int32_t G, int32_t Dm, float temperature, float eps, void* stream,
+                                bool large) {
     if (!out || !work || G <= 0) return CLV_ERR_ARG;
     if (!sim_mat && (!video || !text || Dm <= 0 || temperature <= 0.f || eps <= 0.f)) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -749,17 +1032,36 @@ extern "C" int clv_normsoftmax_fwd(const float* video, const float* text, const 
                            eps);
         int rc = clv_check_launch();
         if (rc) return rc;
-        rc = nce_gemm(W.en, W.en + (int64_t)G * Dm, W.sim, G, G, Dm, Dm, Dm, G, 1, 0, 0, 0, 1.0f / temperature, st);
+        rc = nce_gemm(W.en, W.en + (int64_t)G * Dm, W.sim, G, G, Dm, Dm, Dm, G, 1, 0, 0, 0, 1.0f / temperature, st, 1, 0,
+                      large);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(ns_loss_kernel, dim3(1), dim3(1024), 0, st, W, sim_mat ? sim_mat : (const float*)W.sim, out,
-                       (int)G);
+    const float* sim = sim_mat ? sim_mat : (const float*)W.sim;
+    if (!large) {
+        hipLaunchKernelGGL(ns_loss_kernel, dim3(1), dim3(1024), 0, st, W, sim, out, (int)G);
+        return clv_check_launch();
+    }
+    hipLaunchKernelGGL(ns_lse_rows_kernel, dim3((G + 3) / 4), dim3(256), 0, st, W, sim, (int)G);
+    int rc = clv_check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(ns_lse_cols_kernel, dim3((G + 63) / 64, 1), dim3(64 * LSE_COL_WAVES), 0, st, W, sim, (int)G);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(ns_finish_kernel, dim3(1), dim3(256), 0, st, W, out, (int)G);
     return clv_check_launch();
 }
 
-extern "C" int clv_normsoftmax_bwd(const float* sim_mat, const float* dout, const float* work, float* dvideo,
-                                   float* dtext, float* dsim, int32_t G, int32_t Dm, float temperature,
-                                   void* stream) {
+extern "C" int clv_normsoftmax_fwd(const float* video, const float* text, const float* sim_mat, float* out,
+                                   float* work, int32_t G, int32_t Dm, float temperature, float eps, void* stream) {
+    return normsoftmax_fwd_impl(video, text, sim_mat, out, work, G, Dm, temperature, eps, stream, false);
+}
+extern "C" int clv_normsoftmax_fwd_large(const float* video, const float* text, const float* sim_mat, float* out,
+                                         float* work, int32_t G, int32_t Dm, float temperature, float eps, void* stream) {
+    return normsoftmax_fwd_impl(video, text, sim_mat, out, work, G, Dm, temperature, eps, stream, true);
+}
+
+static int normsoftmax_bwd_impl(const float* sim_mat, const float* dout, const float* work, float* dvideo,
+                                float* dtext, float* dsim, int32_t G, int32_t Dm, float temperature, void* stream,
+                                bool large) {
     if (!dout || !work || G <= 0) return CLV_ERR_ARG;
     if (sim_mat ? !dsim : (!dvideo || !dtext || Dm <= 0 || temperature <= 0.f)) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -773,10 +1075,21 @@ extern "C" int clv_normsoftmax_bwd(const float* sim_mat, const float* dout, cons
     if (rc || sim_mat) return rc;
     const float it = 1.0f / temperature;
     // d en_v[i][d] = sum_j dsim[i][j] en_t[j][d] / t ;  d en_t[j][d] = sum_i dsim[i][j] en_v[i][d] / t
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st);
+    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
     if (rc) return rc;
-    rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st);
+    rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
     if (rc) return rc;
     hipLaunchKernelGGL(ns_norm_bwd_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, W, dvideo, dtext, (int)G, (int)Dm);
     return clv_check_launch();
+}
+
+extern "C" int clv_normsoftmax_bwd(const float* sim_mat, const float* dout, const float* work, float* dvideo,
+                                   float* dtext, float* dsim, int32_t G, int32_t Dm, float temperature,
+                                   void* stream) {
+    return normsoftmax_bwd_impl(sim_mat, dout, work, dvideo, dtext, dsim, G, Dm, temperature, stream, false);
+}
+extern "C" int clv_normsoftmax_bwd_large(const float* sim_mat, const float* dout, const float* work, float* dvideo,
+                                         float* dtext, float* dsim, int32_t G, int32_t Dm, float temperature,
+                                         void* stream) {
+    return normsoftmax_bwd_impl(sim_mat, dout, work, dvideo, dtext, dsim, G, Dm, temperature, stream, true);
 }

@@ -14,7 +14,9 @@ DefaultOptimizerConstructor + AdamW (pretrain_webvid_cc3m.py:129-137), Fp16Optim
   no host synchronisation — the reference syncs the host once per parameter for its overflow
   check (fp16_utils.py:328-349); bf16 needs no loss scaling, non-finite norms skip the step;
 * statically unused parameters (BERT pooler, the fusion model's own embeddings — the reason
-  the reference needs find_unused_parameters=True) are detected on a dry run and excluded.
+  the reference needs find_unused_parameters=True) are detected on a dry run and excluded;
+* ``virtual_ranks=k``: one optimizer step on k micro-batches whose contrastive losses see all k * B rows — what a k-rank
+  DDP job of the reference computes, on one device (``CloverEngine.forward_backward``).
 """
 import math
 
@@ -204,8 +206,9 @@ class _Segment:
 class CloverEngine:
     def __init__(self, model, sample_batch, lr=5e-5, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.005,
                  paramwise_cfg=None, grad_clip=15.0, max_iters=100000, warmup_iters=0, min_lr_ratio=1e-3,
-                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None):
+                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None, virtual_ranks=1):
         self.model = model
+        self.virtual_ranks = int(virtual_ranks)
         # Loss scaling (mmcv_Fp16OptimizerHook.py:33-50,96-149; `fp16 = dict(loss_scale='dynamic')` in the headline config,
         # pretrain_webvid_cc3m.py:21).  `loss_scale` takes what the hook takes: a float (static), 'dynamic'
         # (LossScaler(mode='dynamic'): 2**32, factor 2, window 1000) or a dict of LossScaler arguments; None = the build's
@@ -245,6 +248,11 @@ class CloverEngine:
         if device.type != 'cuda':
             raise RuntimeError('CloverEngine drives the HIP kernels: move the model to an MI355X first (there is no '
                                f'CPU path; got parameters on {device})')
+        self._device = device
+        if self.virtual_ranks < 1:
+            raise ValueError(f'virtual_ranks must be >= 1, got {virtual_ranks}')
+        if self.virtual_ranks > 1:
+            self._check_virtual_ranks(model, sample_batch)
         pw = paramwise_cfg or dict(norm_decay_mult=0.0, bias_decay_mult=0.0,
                                    custom_keys={'absolute_pos_embed': dict(decay_mult=0.),
                                                 'relative_position_bias_table': dict(decay_mult=0.)})
@@ -333,6 +341,27 @@ class CloverEngine:
         self._setup_first_touch(sample_batch)
         self._setup_fused_norm()
 
+    def _check_virtual_ranks(self, model, sample_batch):
+        """What a virtual-rank step cannot reproduce is refused with its reason."""
+        k = self.virtual_ranks
+        if not isinstance(sample_batch, dict):
+            raise ValueError(f'virtual_ranks={k}: sample_batch is ONE micro-batch (a dict), the geometry of all {k}')
+        if collectives_active():
+            raise NotImplementedError(f'virtual_ranks={k} in a data-parallel job: virtual ranks times real ranks is not '
+                                      'implemented (the global batch would be world * k * B rows)')
+        if getattr(model, 'is_qa', False):
+            raise NotImplementedError(f'virtual_ranks={k}: the video_qa / FIB tasks have no loss shared between samples, '
+                                      'so there is nothing a larger global batch would change')
+        if not hasattr(model, 'encode') or not hasattr(model, 'contrastive_losses'):
+            raise NotImplementedError(f'virtual_ranks={k} needs a recognizer with the encode / contrastive_losses split '
+                                      f'(CloverPretrain, CloverFinetune(task="retrieval")); got {type(model).__name__}')
+        from .nn import BatchNorm1d
+        bn = [n for n, m in model.named_modules() if isinstance(m, BatchNorm1d)]
+        if bn:
+            raise NotImplementedError(f'virtual_ranks={k}: {bn[0]} is a BatchNorm1d; per-micro-batch statistics are not the '
+                                      "reference's SyncBN over the global batch, and the recomputed forward would move the "
+                                      'running statistics twice')
+
     def _setup_fused_norm(self):
         """One-rank jobs: the first-touch weight gradients (most of the parameters: each is written by exactly one launch per
         step) deliver their sum of squares from the kernel that writes them (ops.linear_wgrad: flag bit 2 of the grouped /
@@ -341,7 +370,7 @@ class CloverEngine:
         that of the REDUCED gradients (mmcv_Fp16OptimizerHook.py:119-131).  CLOVER_FUSED_NORM=0 switches it off."""
         fresh = getattr(self, '_fresh_sinks', None)
         if (not fresh or self.reducer.active or self.wire is not None or os.environ.get('CLOVER_FUSED_NORM', '1') != '1'
-                or not self.segments[0].flat_g.is_cuda):
+                or not self.segments[0].flat_g.is_cuda or self.virtual_ranks > 1):
             return
         slots = self.sumsq[16:]
         tables = []
@@ -372,8 +401,8 @@ class CloverEngine:
         A third pass with the final marking must reproduce every gradient, otherwise the scheme is switched off."""
         self._ft = ops.FirstTouch()
         self.first_touch_params = 0
-        if os.environ.get('CLOVER_GRAD_FIRST_TOUCH', '1') != '1':
-            return
+        if os.environ.get('CLOVER_GRAD_FIRST_TOUCH', '1') != '1' or self.virtual_ranks > 1:
+            return                             # (virtual ranks: k backward passes ADD into the slabs, nothing may store)
         sinks = {}                             # data_ptr -> (sink tensor, segment index, slab offset, numel)
         for si, seg in enumerate(self.segments):
             for q, off in zip(seg.params, seg.offsets):
@@ -508,7 +537,12 @@ class CloverEngine:
         return out
 
     def step(self, batch):
-        """forward + backward + gradient all-reduce + clip + AdamW.  Returns train_step's dict."""
+        """forward + backward + gradient all-reduce + clip + AdamW.  Returns train_step's dict.  With ``virtual_ranks=k``
+        ``batch`` is a sequence of k micro-batches of one geometry (forward_backward)."""
+        if self.virtual_ranks > 1:
+            out = self.forward_backward(batch)
+            self.optimizer_step()
+            return out
         self.reducer.begin_step()
         if self.graph is not None:
             sig = self._signature(batch)
@@ -529,6 +563,138 @@ class CloverEngine:
         self.optimizer_step()
         self._mark('optimizer')
         return out
+
+    # ------------------------------------------------------------------ virtual ranks
+    def forward_backward(self, batches):
+        """Everything of step() except optimizer_step(); returns train_step's dict.
+
+        ``virtual_ranks=k``: ``batches`` is a sequence of k batch dicts of one geometry; micro-batch j is rows
+        [j B, (j + 1) B) of the global batch, rank-major as all_gather orders them.  The step computes what a k-rank DDP job
+        of the reference computes: the contrastive / rank losses ONCE on all k B rows, each micro-batch's rank-local loss
+        (mlm_loss) on its own rows, and the gradient  1/k sum_j [J_j^T dLc/dE[jB:(j+1)B] + grad L_local,j]  — including the
+        1/W effect of the gather's local-slice backward.  A micro-batch is a rank whose all-gather is a copy:
+
+        * pass 1: every micro-batch runs ``encode`` (the captured forward graph, or eagerly under no_grad); its embeddings
+          and local loss are stashed, and so is the RNG state its dropout / DropPath draws start from;
+        * the loss section runs once, eagerly, on the [k B, 6, D] stash, with the device loss scale as root gradient;
+        * pass 2: the last micro-batch's activations are still alive, so it goes backward at once; every other one restores
+          its RNG state, recomputes its forward (same masks) and goes backward with its slice of d E.  All k backward passes
+          ADD into the gradient slabs (an engine with virtual ranks has neither first-touch stores nor the fused norm), and
+          ``optimizer_step`` divides by k next to the loss scale.
+
+        Afterwards the slab views (``param.grad``) hold loss_scale * sum_j.  Logged values are what rank 0 of the reference
+        logs after its all-reduce: the shared contrastive values, the mean of the k local ones, ``loss`` their sum;
+        ``num_samples`` counts the k B samples of the step."""
+        if self.virtual_ranks == 1:
+            batch = batches if isinstance(batches, dict) else batches[0]
+            self.reducer.begin_step()
+            if self.graph is not None:
+                sig = self._signature(batch)
+                if sig != self._active_sig:
+                    if sig in self._captures:
+                        self._activate(sig)
+                    else:
+                        self.capture(batch)
+                out = self._graphed_forward_backward(batch)
+            else:
+                self.reducer.prepacked = frozenset()
+                self._ft.done.clear()
+                out = self.model.train_step(batch, None)
+                self._backward(lambda: out['loss'].backward())
+            self.finish_backward()
+            return out
+        k = self.virtual_ranks
+        if isinstance(batches, dict) or len(batches) != k:
+            raise ValueError(f'virtual_ranks={k}: a step takes a sequence of {k} micro-batches, got '
+                             + ('one batch dict' if isinstance(batches, dict) else f'{len(batches)}'))
+        sig = self._signature(batches[0])
+        for j in range(1, k):
+            if self._signature(batches[j]) != sig:
+                raise ValueError(f'virtual_ranks={k}: micro-batch {j} has another geometry than micro-batch 0 '
+                                 f'({self._signature(batches[j])} vs {sig}); the k micro-batches share one set of graphs')
+        self.reducer.begin_step()
+        self.reducer.prepacked = frozenset()
+        graphed = self.graph is not None
+        if graphed and sig != self._active_sig:
+            if sig in self._captures:
+                self._activate(sig)
+            else:
+                self.capture(batches[0])
+        model = self.model
+        keys = tuple(getattr(model, 'CLV_ENCODE_KEYS', ('token_ids', 'input_mask', 'mlm_label', 'v_token_mask')))
+        drop_ctr = ops._dropout_counter(self._device)
+
+        def rng_save():
+            return torch.cuda.get_rng_state(self._device), drop_ctr.clone()
+
+        def rng_restore(st):
+            torch.cuda.set_rng_state(st[0], self._device)
+            drop_ctr.copy_(st[1])
+
+        def forward(j, grad):
+            """encode of micro-batch j -> (emb, mlm): the static outputs of the forward graph, or eager tensors."""
+            b = batches[j]
+            if graphed:
+                for name, v in self._static_batch.items():
+                    if b[name] is not v:
+                        v.copy_(b[name], non_blocking=True)
+                self.graph.replay()
+                return self._static_emb, self._static_mlm
+            with torch.enable_grad() if grad else torch.no_grad():
+                return model.encode(b['imgs'], **{name: b[name] for name in keys})
+
+        def backward(live, demb, dmlm):
+            if graphed:
+                self._static_demb.copy_(demb)
+                if self._static_dmlm is not None:
+                    self._static_dmlm.copy_(dmlm)
+                self._replay_backward()
+            else:
+                emb, mlm = live
+                roots, grads = [emb], [demb.to(emb.dtype)]
+                if mlm is not None:
+                    roots.append(mlm)
+                    grads.append(dmlm.to(mlm.dtype).reshape(mlm.shape))
+                self._backward(lambda: torch.autograd.backward(roots, grads))
+
+        # ---- pass 1
+        rng, embs, mlms, live = [], [], [], None
+        for j in range(k):
+            rng.append(rng_save())
+            live = forward(j, grad=j == k - 1)
+            embs.append(live[0].detach().float().clone() if graphed else live[0].detach().float())
+            if live[1] is not None:
+                mlms.append(live[1].detach().float().reshape(()).clone())
+        rng_end = rng_save()
+        self._vr_emb = embs
+        # ---- the loss section, once, on all k * B rows
+        E = torch.cat(embs, 0).requires_grad_()
+        mlm = torch.stack(mlms).mean().requires_grad_() if mlms else None     # rank 0 logs the mean of the k local values
+        import inspect
+        if 'gathered' in inspect.signature(model.contrastive_losses).parameters:
+            losses = model.contrastive_losses(None, mlm, gathered=E)
+        else:
+            losses = model.contrastive_losses(E, mlm)
+        loss, log_vars = self._parse_root_scaled(losses)
+        loss.backward(gradient=self._root_gradient(loss))
+        B = embs[0].shape[0]
+        dE = E.grad
+        dmlm = mlm.grad if mlm is not None else None          # d loss / d L_local,j = the root gradient, for every j
+        # ---- pass 2: the live micro-batch first, then every other one recomputed under its own masks
+        self._vr_emb_recomputed = {}
+        for j in [k - 1] + list(range(k - 1)):
+            if j != k - 1:
+                rng_restore(rng[j])
+                live = forward(j, grad=True)
+                if self._vr_keep_recomputed:
+                    self._vr_emb_recomputed[j] = live[0].detach().float().clone()
+            backward(live, dE[j * B:(j + 1) * B], dmlm)
+            live = None
+        rng_restore(rng_end)                                   # the next step draws new masks, not micro-batch 1's again
+        self.finish_backward()
+        return dict(loss=loss.detach(), log_vars=log_vars, num_samples=k * len(next(iter(batches[0].values()))))
+
+    _vr_keep_recomputed = False                # tests: keep the embeddings the recomputed forwards produce (_vr_emb_recomputed)
 
     def finish_backward(self):
         """Close a backward pass: clear the first-touch slots an EAGER backward did not reach, THEN complete the gradient
@@ -819,10 +985,12 @@ class CloverEngine:
         """The section between the two encode graphs — contrastive / rank losses on the gathered embeddings, the loss
         sum and its backward down to d emb / d mlm — as a hipGraph over a static gathered tensor.  The all-gather that
         fills it and the all-reduce of the logged scalars stay eager (no RCCL call is ever captured); the gather's
-        backward is the local slice (gather_loss.py:64-72), taken inside the graph."""
+        backward is the local slice (gather_loss.py:64-72), taken inside the graph.  CLOVER_LOSS_GRAPH=1 is ignored with
+        virtual_ranks > 1: that loss section runs once per k replays, on a tensor k times the captured one."""
         import inspect
         model = self.model
-        if (os.environ.get('CLOVER_LOSS_GRAPH', '0') != '1' or not hasattr(model, 'contrastive_losses')
+        if (os.environ.get('CLOVER_LOSS_GRAPH', '0') != '1' or self.virtual_ranks > 1
+                or not hasattr(model, 'contrastive_losses')
                 or 'gathered' not in inspect.signature(model.contrastive_losses).parameters
                 or not getattr(getattr(model, 'ssl_loss', None), 'equal_batch', False)):
             return None, None
@@ -877,7 +1045,8 @@ class CloverEngine:
                                        'engine.reducer.finish()')
                 torch._foreach_zero_(stale)
         self._stale_cleared = False
-        gscale = 1.0 / self.world      # DDP averages the summed gradients (the loss scale is divided out on the device)
+        # DDP averages the summed gradients (the loss scale is divided out on the device); k virtual ranks are k more ranks
+        gscale = 1.0 / (self.world * self.virtual_ranks)
         grads = self.wire if self.wire is not None else [seg.flat_g for seg in self.segments]   # reduced gradients
         fused = self._norm_tables is not None
         if fused and self._norm_state.dirty:   # a sink got a second gradient this step (ops.linear_wgrad): recompute it all

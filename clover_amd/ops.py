@@ -2255,6 +2255,22 @@ def focal_ce_masked(logits, labels, gamma=2.0):
 
 
 # --------------------------------------------------------------------------- InfoNCE + rank
+# The loss section has two sets of kernels (csrc/losses.hip): one workgroup per evaluation for a device batch, and from
+# clv_infonce_large_min_g() rows on — the global batch of a virtual-rank step — log-sum-exp kernels spread over the device
+# with LDS-tiled GEMMs.  NCE_FORCE_LARGE: None = dispatch by the row count; True / False pins one set (the timing tool and
+# the tests that compare the two).
+NCE_FORCE_LARGE = None
+
+
+def nce_large_min_g():
+    return int(_lib.lib().clv_infonce_large_min_g())
+
+
+def _nce_fn(name, G):
+    large = NCE_FORCE_LARGE if NCE_FORCE_LARGE is not None else G >= nce_large_min_g()
+    return getattr(_lib.lib(), name + '_large' if large else name), bool(large)
+
+
 class _InfoNCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e0, e1, e2, e3, temperature, margin):
@@ -2264,8 +2280,9 @@ class _InfoNCE(torch.autograd.Function):
         L = _lib.lib()
         work = torch.empty(L.clv_infonce_work_floats(G, Dm), device=e0.device, dtype=torch.float32)
         out = torch.empty(2, device=e0.device, dtype=torch.float32)
-        check(L.clv_infonce_fwd(_ptr(es[0]), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), _ptr(out), _ptr(work), G, Dm, Dm,
-                                float(temperature), float(margin), _stream()), 'clv_infonce_fwd')
+        fwd, ctx.large = _nce_fn('clv_infonce_fwd', G)
+        check(fwd(_ptr(es[0]), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), _ptr(out), _ptr(work), G, Dm, Dm,
+                  float(temperature), float(margin), _stream()), 'clv_infonce_fwd')
         ctx.save_for_backward(*es, work)
         ctx.cfg = (G, Dm, float(temperature), float(margin), [e.dtype for e in (e0, e1, e2, e3)])
         return out[0], out[1]
@@ -2276,9 +2293,10 @@ class _InfoNCE(torch.autograd.Function):
         G, Dm, temp, margin, dts = ctx.cfg
         dout = torch.stack([dnce.float().reshape(()), drank.float().reshape(())]).contiguous()
         ds = [torch.empty_like(e0) for _ in range(4)]
-        check(_lib.lib().clv_infonce_bwd(_ptr(e0), _ptr(e1), _ptr(e2), _ptr(e3), _ptr(dout), _ptr(work), _ptr(ds[0]),
-                                         _ptr(ds[1]), _ptr(ds[2]), _ptr(ds[3]), G, Dm, Dm, temp, margin, _stream()),
-              'clv_infonce_bwd')
+        L = _lib.lib()
+        check((L.clv_infonce_bwd_large if ctx.large else L.clv_infonce_bwd)(
+            _ptr(e0), _ptr(e1), _ptr(e2), _ptr(e3), _ptr(dout), _ptr(work), _ptr(ds[0]), _ptr(ds[1]), _ptr(ds[2]),
+            _ptr(ds[3]), G, Dm, Dm, temp, margin, _stream()), 'clv_infonce_bwd')
         return ds[0].to(dts[0]), ds[1].to(dts[1]), ds[2].to(dts[2]), ds[3].to(dts[3]), None, None
 
 
@@ -2297,8 +2315,9 @@ class _InfoNCEPacked(torch.autograd.Function):
         out = torch.empty(2, device=packed.device, dtype=torch.float32)
         base = packed.data_ptr()
         es = [C.c_void_p(base + 4 * Dm * int(sl)) for sl in slots]
-        check(L.clv_infonce_fwd(*es, _ptr(out), _ptr(work), G, Dm, k * Dm, float(temperature), float(margin),
-                                _stream()), 'clv_infonce_fwd')
+        fwd, ctx.large = _nce_fn('clv_infonce_fwd', G)
+        check(fwd(*es, _ptr(out), _ptr(work), G, Dm, k * Dm, float(temperature), float(margin), _stream()),
+              'clv_infonce_fwd')
         ctx.save_for_backward(work)
         ctx.cfg = (G, k, Dm, tuple(int(sl) for sl in slots), float(temperature), float(margin))
         return out[0], out[1]
@@ -2311,8 +2330,9 @@ class _InfoNCEPacked(torch.autograd.Function):
         dp = torch.zeros(G, k, Dm, device=work.device, dtype=torch.float32)
         base = dp.data_ptr()
         ds = [C.c_void_p(base + 4 * Dm * sl) for sl in slots]
-        check(_lib.lib().clv_infonce_bwd(None, None, None, None, _ptr(dout), _ptr(work), *ds, G, Dm, k * Dm, temp,
-                                         margin, _stream()), 'clv_infonce_bwd')
+        L = _lib.lib()
+        check((L.clv_infonce_bwd_large if ctx.large else L.clv_infonce_bwd)(
+            None, None, None, None, _ptr(dout), _ptr(work), *ds, G, Dm, k * Dm, temp, margin, _stream()), 'clv_infonce_bwd')
         return dp, None, None, None
 
 
@@ -2331,8 +2351,9 @@ class _InfoNCEPair(torch.autograd.Function):
         slots = (C.c_int32 * 8)(*[int(v) for v in tuple(slots_a) + tuple(slots_b)])
         work = torch.empty(2 * L.clv_infonce_work_floats(G, Dm), device=packed.device, dtype=torch.float32)
         out = torch.empty(4, device=packed.device, dtype=torch.float32)
-        check(L.clv_infonce_pair_fwd(_ptr(packed), slots, _ptr(out), _ptr(work), G, k, Dm, float(temperature),
-                                     float(margin), _stream()), 'clv_infonce_pair_fwd')
+        fwd, ctx.large = _nce_fn('clv_infonce_pair_fwd', G)
+        check(fwd(_ptr(packed), slots, _ptr(out), _ptr(work), G, k, Dm, float(temperature), float(margin), _stream()),
+              'clv_infonce_pair_fwd')
         ctx.save_for_backward(work)
         ctx.cfg = (G, k, Dm, slots, float(temperature), float(margin))
         return out[0], out[1], out[2], out[3]
@@ -2345,8 +2366,9 @@ class _InfoNCEPair(torch.autograd.Function):
         ds = [d if d is None or d.dtype == torch.float32 else d.float() for d in douts]
         dout = (C.c_void_p * 4)(*[None if d is None else d.data_ptr() for d in ds])
         dp = torch.empty(G, k, Dm, device=work.device, dtype=torch.float32)
-        check(_lib.lib().clv_infonce_pair_bwd(dout, _ptr(work), slots, _ptr(dp), G, k, Dm, temp, margin, _stream()),
-              'clv_infonce_pair_bwd')
+        L = _lib.lib()
+        check((L.clv_infonce_pair_bwd_large if ctx.large else L.clv_infonce_pair_bwd)(
+            dout, _ptr(work), slots, _ptr(dp), G, k, Dm, temp, margin, _stream()), 'clv_infonce_pair_bwd')
         return dp, None, None, None, None
 
 
@@ -2389,8 +2411,9 @@ class _NormSoftmax(torch.autograd.Function):
         dev = (x if x is not None else v).device
         work = torch.empty(L.clv_normsoftmax_work_floats(G, Dm), device=dev, dtype=torch.float32)
         out = torch.empty(1, device=dev, dtype=torch.float32)
-        check(L.clv_normsoftmax_fwd(_ptr(v), _ptr(t), _ptr(x), _ptr(out), _ptr(work), G, Dm, float(temperature),
-                                    float(eps), _stream()), 'clv_normsoftmax_fwd')
+        fwd, ctx.large = _nce_fn('clv_normsoftmax_fwd', G)
+        check(fwd(_ptr(v), _ptr(t), _ptr(x), _ptr(out), _ptr(work), G, Dm, float(temperature), float(eps), _stream()),
+              'clv_normsoftmax_fwd')
         ctx.save_for_backward(work, *([x] if x is not None else []))
         ctx.cfg = (G, Dm, float(temperature), None if x is not None else (video.dtype, text.dtype),
                    sim_mat.dtype if x is not None else None)
@@ -2402,14 +2425,15 @@ class _NormSoftmax(torch.autograd.Function):
         G, Dm, temp, dts, sdt = ctx.cfg
         dout = _c(dloss.float().reshape(1))
         L = _lib.lib()
+        bwd = L.clv_normsoftmax_bwd_large if ctx.large else L.clv_normsoftmax_bwd
         if rest:
             dsim = torch.empty_like(rest[0])
-            check(L.clv_normsoftmax_bwd(_ptr(rest[0]), _ptr(dout), _ptr(work), None, None, _ptr(dsim), G, Dm, temp,
+            check(bwd(_ptr(rest[0]), _ptr(dout), _ptr(work), None, None, _ptr(dsim), G, Dm, temp,
                                         _stream()), 'clv_normsoftmax_bwd')
             return None, None, dsim.to(sdt), None, None
         dv = torch.empty(G, Dm, device=work.device, dtype=torch.float32)
         dt = torch.empty_like(dv)
-        check(L.clv_normsoftmax_bwd(None, _ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), None, G, Dm, temp, _stream()),
+        check(bwd(None, _ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), None, G, Dm, temp, _stream()),
               'clv_normsoftmax_bwd')
         return dv.to(dts[0]), dt.to(dts[1]), None, None, None
 

@@ -115,12 +115,39 @@ def parse_cfg_options(items):
 def scaled_lr(cfg, world_size):
     """tools/train.py:160-166 — if the optimizer config carries ``base_lr`` it is REMOVED and
     ``lr = base_lr * videos_per_gpu * world_size`` is set, with videos_per_gpu read from the TOP level of the
-    config (``cfg.get('videos_per_gpu', 1)``, not ``cfg.data``), exactly as the reference does."""
+    config (``cfg.get('videos_per_gpu', 1)``, not ``cfg.data``), exactly as the reference does.  The rule is base_lr times
+    the GLOBAL batch: ``virtual_ranks = k`` (top level) counts as k more ranks."""
     opt = cfg.optimizer
     if 'base_lr' in opt:
         base_lr = opt.pop('base_lr')
-        opt['lr'] = base_lr * cfg.get('videos_per_gpu', 1) * world_size
+        opt['lr'] = base_lr * cfg.get('videos_per_gpu', 1) * world_size * int(cfg.get('virtual_ranks', 1) or 1)
     return opt.get('lr')
+
+
+class GroupedLoader:
+    """Lists of k consecutive batches of ``loader`` — the k micro-batches of one virtual-rank step
+    (``CloverEngine(virtual_ranks=k).step``), in the loader's order: micro-batch j of step i is batch ``i * k + j``.
+    ``len`` is ``len(loader) // k``; a remainder is dropped, said once in one printed line."""
+
+    def __init__(self, loader, k, printer=print):
+        if int(k) < 1:
+            raise ValueError(f'GroupedLoader: k must be >= 1, got {k}')
+        self.loader, self.k = loader, int(k)
+        rest = len(loader) % self.k
+        if rest and printer is not None:
+            printer(f'virtual_ranks={self.k}: the last {rest} of {len(loader)} batches per epoch do not fill a step and '
+                    'are dropped')
+
+    def __len__(self):
+        return len(self.loader) // self.k
+
+    def __iter__(self):
+        group = []
+        for batch in self.loader:
+            group.append(batch)
+            if len(group) == self.k:
+                yield group
+                group = []
 
 
 # --------------------------------------------------------------------------- runner

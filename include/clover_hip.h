@@ -449,6 +449,29 @@ int clv_normsoftmax_fwd(const float* video, const float* text, const float* sim_
 int clv_normsoftmax_bwd(const float* sim_mat, const float* dout, const float* work, float* dvideo, float* dtext,
                         float* dsim, int32_t G, int32_t Dm, float temperature, void* stream);
 
+/* The same six entry points for a GLOBAL batch (virtual ranks: G = k * B rows, 1024 at the reference's headline
+ * configuration).  The functions above compute every log-sum-exp in ONE workgroup; these spread them over the device — one
+ * wave per exclusive row, 64 adjacent columns per workgroup, one pass each with a running (max, sum) — reduce the per-row
+ * terms in a fixed order in a finish kernel (no float atomics: the losses are bit-reproducible from run to run) and run
+ * their GEMMs as 64 x 64 LDS tiles.  Arguments, `work` layout and sizes are those of the function without the suffix, so a
+ * `work` either forward filled serves either backward.  clv_infonce_large_min_g(): the row count from which the callers
+ * (clover_amd.ops) take these — the measured crossover; below it the functions above run, bit for bit as before. */
+int32_t clv_infonce_large_min_g(void);
+int clv_infonce_fwd_large(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
+                          float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
+                          void* stream);
+int clv_infonce_bwd_large(const float* e0, const float* e1, const float* e2, const float* e3,
+                          const float* dout, const float* work, float* d0, float* d1, float* d2, float* d3,
+                          int32_t G, int32_t Dm, int32_t ldd, float temperature, float margin, void* stream);
+int clv_infonce_pair_fwd_large(const float* packed, const int32_t* slots, float* out, float* work, int32_t G, int32_t k,
+                               int32_t Dm, float temperature, float margin, void* stream);
+int clv_infonce_pair_bwd_large(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
+                               int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream);
+int clv_normsoftmax_fwd_large(const float* video, const float* text, const float* sim_mat, float* out, float* work,
+                              int32_t G, int32_t Dm, float temperature, float eps, void* stream);
+int clv_normsoftmax_bwd_large(const float* sim_mat, const float* dout, const float* work, float* dvideo, float* dtext,
+                              float* dsim, int32_t G, int32_t Dm, float temperature, void* stream);
+
 /* ------------------------------------------------------------------ optimizer
  * Grad-norm (clip_grad_norm_, mmcv_Fp16OptimizerHook.py:127-137) + AdamW step on flat
  * buffers (optimizer cfg pretrain_webvid_cc3m.py:129-137).

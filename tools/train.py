@@ -54,9 +54,22 @@ class SyntheticLoader:
             yield self.batches[i % len(self.batches)]
 
 
+def engine_kwargs(cfg, lr, half_f16=True):
+    """The CloverEngine arguments a config asks for (optimizer, grad clip, loss scaler, virtual_ranks)."""
+    opt = cfg.optimizer
+    return dict(lr=lr, betas=tuple(opt.get('betas', (0.9, 0.999))), eps=opt.get('eps', 1e-8),
+                weight_decay=opt.get('weight_decay', 0.0), paramwise_cfg=opt.get('paramwise_cfg'),
+                grad_clip=(cfg.get('optimizer_config', {}).get('grad_clip') or {}).get('max_norm', 0.0),
+                # `fp16 = dict(loss_scale=...)` of a reference config (pretrain_webvid_cc3m.py:21) -> the engine's
+                # device-resident loss scaler (fp16 build; the bf16 build keeps its default: none)
+                loss_scale=(cfg.get('fp16') or {}).get('loss_scale') if half_f16 else None,
+                # `virtual_ranks = k`: every optimizer step takes k batches whose contrastive losses see all k * B rows
+                virtual_ranks=int(cfg.get('virtual_ranks', 1) or 1))
+
+
 def main():
     args = parse_args()
-    from clover_amd.runner import (CheckpointHook, CloverRunner, Config, EvalHook, LogHook, LrUpdaterHook,
+    from clover_amd.runner import (CheckpointHook, CloverRunner, Config, EvalHook, GroupedLoader, LogHook, LrUpdaterHook,
                                    parse_cfg_options, scaled_lr)
     import clover_amd
     from clover_amd.engine import CloverEngine
@@ -91,20 +104,17 @@ def main():
     syn = cfg.data['synthetic']
     loaders = [SyntheticLoader(s['length'], cfg.get('videos_per_gpu', 1), s.get('frames', 8), s.get('tokens', 32),
                                1000 * (i + 1) + rank, dev, qa=s.get('qa')) for i, s in enumerate(syn)]
-    opt, lrc = cfg.optimizer, cfg.lr_config
-    engine = CloverEngine(model, next(iter(loaders[0])), lr=lr, betas=tuple(opt.get('betas', (0.9, 0.999))),
-                          eps=opt.get('eps', 1e-8), weight_decay=opt.get('weight_decay', 0.0),
-                          paramwise_cfg=opt.get('paramwise_cfg'),
-                          grad_clip=(cfg.get('optimizer_config', {}).get('grad_clip') or {}).get('max_norm', 0.0),
-                          # `fp16 = dict(loss_scale=...)` of a reference config (pretrain_webvid_cc3m.py:21) -> the engine's
-                          # device-resident loss scaler (fp16 build; the bf16 build keeps its default: none)
-                          loss_scale=(cfg.get('fp16') or {}).get('loss_scale') if clover_amd._lib.HALF_F16 else None)
+    lrc = cfg.lr_config
+    kw = engine_kwargs(cfg, lr, clover_amd._lib.HALF_F16)
+    engine = CloverEngine(model, next(iter(loaders[0])), **kw)      # (virtual ranks: built and captured on ONE micro-batch)
     if lrc.get('policy', 'CosineAnnealing') != 'CosineAnnealing' or lrc.get('by_epoch', True):
         raise NotImplementedError('lr_config: only CosineAnnealing with by_epoch=False (the reference recipe)')
     if cfg.get('hip_graph', True):                       # static shapes: replay the step as hipGraphs
         first = next(iter(loaders[0]))
         engine.dry_step(first)                           # no optimizer step: training starts from the initial weights
         engine.capture(first)
+    if kw['virtual_ranks'] > 1:                          # lists of k batches per step: runner.iter counts optimizer steps
+        loaders = [GroupedLoader(ld, kw['virtual_ranks'], printer=print if rank == 0 else None) for ld in loaders]
     runner = CloverRunner(engine, model=model, work_dir=cfg.work_dir, max_epochs=cfg.total_epochs,
                           meta=dict(config_name=os.path.basename(args.config), seed=args.seed))
     # the LR follows runner.iter (batch indices), not the count of optimizer steps (two per index with two loaders)
