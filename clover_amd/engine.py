@@ -16,7 +16,9 @@ DefaultOptimizerConstructor + AdamW (pretrain_webvid_cc3m.py:129-137), Fp16Optim
 * statically unused parameters (BERT pooler, the fusion model's own embeddings — the reason
   the reference needs find_unused_parameters=True) are detected on a dry run and excluded;
 * ``virtual_ranks=k``: one optimizer step on k micro-batches whose contrastive losses see all k * B rows — what a k-rank
-  DDP job of the reference computes, on one device (``CloverEngine.forward_backward``).
+  DDP job of the reference computes, on one device (``CloverEngine.forward_backward``);
+* ``ema_enable`` / ``ema_update`` / ``ema_swap``: the reference's ``ema_hook`` (mmaction/core/hooks/ema.py) — an fp32 moving
+  average of the weights in a slab of its own per segment, updated and exchanged with the weights by one HIP launch each.
 """
 import math
 
@@ -243,6 +245,9 @@ class CloverEngine:
         self.graph_bwd_video = None
         self.graph_bwd_text = None
         self._captures = {}                    # batch-shape signature -> the captured graphs + their static tensors
+        self._ema_table = None                 # ops.EmaTable once ema_enable() ran
+        self.ema_names = {}                    # state_dict name -> its ``ema_*`` buffer name
+        self.ema_swapped = False               # True: the parameters hold the average, the ``ema_*`` buffers the weights
         self._active_sig = None
         device = next(model.parameters()).device
         if device.type != 'cuda':
@@ -539,6 +544,7 @@ class CloverEngine:
     def step(self, batch):
         """forward + backward + gradient all-reduce + clip + AdamW.  Returns train_step's dict.  With ``virtual_ranks=k``
         ``batch`` is a sequence of k micro-batches of one geometry (forward_backward)."""
+        self._refuse_swapped('step')
         if self.virtual_ranks > 1:
             out = self.forward_backward(batch)
             self.optimizer_step()
@@ -585,6 +591,7 @@ class CloverEngine:
         Afterwards the slab views (``param.grad``) hold loss_scale * sum_j.  Logged values are what rank 0 of the reference
         logs after its all-reduce: the shared contrastive values, the mean of the k local ones, ``loss`` their sum;
         ``num_samples`` counts the k B samples of the step."""
+        self._refuse_swapped('forward_backward')
         if self.virtual_ranks == 1:
             batch = batches if isinstance(batches, dict) else batches[0]
             self.reducer.begin_step()
@@ -1030,6 +1037,7 @@ class CloverEngine:
         corrections and Adam's own step count live on the device (``clv_optim_prep``): a step with a non-finite
         gradient norm is skipped there and does not advance Adam's count (mmcv_Fp16OptimizerHook.py:123-141), while
         the LR index moves on like the reference's ``runner.iter``."""
+        self._refuse_swapped('optimizer_step')
         lr = self.current_lr()
         self.lr_iter += 1
         self.step_count += 1
@@ -1071,6 +1079,81 @@ class CloverEngine:
             seg.refresh_transposed()
         self.zero_grads()
         self.last_lr = lr
+
+    # ------------------------------------------------------------------ weight EMA (the reference's ema_hook)
+    def ema_enable(self, skip_buffers=False):
+        """Start keeping an exponential moving average of the weights (mmaction/core/hooks/ema.py:43-62).
+
+        Every segment gets an fp32 slab ``ema`` laid out like ``flat_p`` and initialised to a copy of it (phantom padding
+        rows included: zero, and they stay zero).  Every floating-point entry ``name`` of ``model.state_dict()`` is
+        registered on the model as the buffer ``'ema_' + name.replace('.', '_')`` (the reference's naming, :55-59): a view
+        into the ``ema`` slab for a slab parameter, a plain clone — a LOOSE entry of the kernels' table — for the rest:
+        parameters the step never reaches (``unused_names``), frozen parameters and, unless ``skip_buffers``, float buffers
+        such as BatchNorm1d's running statistics.  So ``state_dict()`` / checkpoints carry the average and
+        ``load_state_dict`` writes into it in place; nothing else needs to know.  Integer and bool buffers
+        (``num_batches_tracked``, index tables) take no part — the reference clones and swaps them without ever updating
+        them, which exchanges equal values.  The average is fp32 over the fp32 masters whatever the 16-bit
+        build; every rank of a data-parallel job keeps its own, identical, copy (no collective)."""
+        if self._ema_table is not None:
+            if bool(skip_buffers) != self._ema_skip_buffers:
+                raise RuntimeError(f'ema_enable(skip_buffers={skip_buffers}): the EMA is already enabled with '
+                                   f'skip_buffers={self._ema_skip_buffers}')
+            return
+        model = self.model
+        param_names = {n for n, _ in model.named_parameters()}
+        state = [(n, t) for n, t in model.state_dict(keep_vars=True).items() if t.dtype.is_floating_point]
+        if skip_buffers:                       # :51-54 — only the parameters then
+            state = [(n, t) for n, t in state if n in param_names]
+        # by address, not by name: a tied tensor appears in state_dict() under every one of its names, and each memory
+        # location may have only ONE entry in the table (one writer per element; a second entry would swap it back)
+        slot = {q.data_ptr(): (sg, off) for sg in self.segments for q, off in zip(sg.params, sg.offsets)}
+        entries, loose = [], {}
+        for sg in self.segments:
+            sg.ema = sg.flat_p.clone()
+            entries.append((sg.flat_p, sg.ema, sg.shadow))
+        for name, t in state:
+            buf_name = 'ema_' + name.replace('.', '_')
+            if t.data_ptr() in slot:
+                sg, off = slot[t.data_ptr()]
+                buf = sg.ema[off:off + t.numel()].view_as(t)
+            elif t.data_ptr() in loose:
+                buf = loose[t.data_ptr()]
+            else:
+                data = t.detach()
+                if data.dtype != torch.float32 or not data.is_contiguous():
+                    raise NotImplementedError(f'ema_enable: {name} ({data.dtype}, contiguous={data.is_contiguous()}) is '
+                                              'outside the slabs and not a contiguous fp32 tensor')
+                buf = loose[t.data_ptr()] = data.clone()
+                entries.append((data, buf, None))
+            model.register_buffer(buf_name, buf)
+            self.ema_names[name] = buf_name
+        self._ema_table = ops.ema_table(entries, self._device)
+        self._ema_skip_buffers = bool(skip_buffers)
+
+    def ema_update(self, momentum):
+        """ema = (1 - momentum) * ema + momentum * weights for the whole model: one launch on the current stream, outside
+        every graph (so ``momentum`` may change each call).  Once per optimizer step, also a skipped one."""
+        if self._ema_table is None:
+            raise RuntimeError('ema_update: call ema_enable() first')
+        if self.ema_swapped:
+            raise RuntimeError('ema_update while the EMA is swapped in: the parameters hold the average itself')
+        ops.ema_update(self._ema_table, momentum)
+
+    def ema_swap(self):
+        """Exchange weights and average IN PLACE (every address a captured graph holds stays valid) and re-derive what
+        the kernels compute from: the 16-bit shadows (written by the swap kernel with AdamW's rounding) and their W^T
+        copies.  Toggles ``ema_swapped``; while it is set the training entry points refuse to run."""
+        if self._ema_table is None:
+            raise RuntimeError('ema_swap: call ema_enable() first')
+        ops.ema_swap(self._ema_table)
+        for sg in self.segments:
+            sg.refresh_transposed()
+        self.ema_swapped = not self.ema_swapped
+
+    def _refuse_swapped(self, what):
+        if self.ema_swapped:
+            raise RuntimeError(f'CloverEngine.{what}() while the EMA weights are swapped in (ema_swapped): it would train '
+                               'the averaged weights; call ema_swap() again first')
 
     def optimizer_state(self):
         """AdamW state for checkpoints: per segment the flat moments + names/offsets, and the step count."""

@@ -2539,6 +2539,76 @@ def adamw_step_dev(p, g, m, v, shadow, state, lr, beta1, beta2, eps, weight_deca
                  float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), _stream()), 'clv_adamw_step_dev')
 
 
+# --------------------------------------------------------------------------- weight EMA (csrc/ema.hip)
+EMA_CHUNK = 4096                           # include/clover_hip.h: CLV_EMA_CHUNK
+
+
+class EmaTable(NamedTuple):
+    """Device tables of clv_ema_update / clv_ema_swap over one list of (p, ema, shadow) tensors (ema_table)."""
+    update: torch.Tensor                   # int64: n_entries x {p, ema, n}, then n_blocks x {entry, start}
+    swap: torch.Tensor                     # int64: n_entries x {p, ema, shadow, n}, then the same block records
+    n_entries: int
+    n_blocks: int
+    numel: int                             # elements of all entries
+    shadow_numel: int                      # ... of the entries with a 16-bit copy
+    tensors: tuple                         # the tensors the tables point into (kept alive with them)
+
+
+def ema_table(entries, device):
+    """Tables for ema_update / ema_swap.  ``entries``: (p, ema) or (p, ema, shadow) tuples — fp32 tensors of equal size,
+    contiguous, on ``device``; ``shadow`` (or None) is the 16-bit compute copy of ``p`` that a swap rewrites.  A whole slab
+    is ONE entry; a loose tensor may have any length and any (4-byte) alignment.  Every entry is cut into chunks of
+    EMA_CHUNK floats, one 256-thread block each."""
+    device = torch.device(device)
+    rows_u, rows_s, blocks, keep, total, shadowed = [], [], [], [], 0, 0
+    for i, ent in enumerate(entries):
+        p, ema = ent[0], ent[1]
+        shadow = ent[2] if len(ent) > 2 else None
+        _need_gpu(p, ema, shadow)
+        n = p.numel()
+        for t, dt, what in ((p, torch.float32, 'p'), (ema, torch.float32, 'ema'), (shadow, BF16, 'shadow')):
+            if t is None:
+                continue
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != p.device:
+                raise ValueError(f'ema_table: entry {i}: {what} must be a contiguous {dt} tensor of {n} elements on '
+                                 f'{p.device}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+        if p.data_ptr() == ema.data_ptr() and n:
+            raise ValueError(f'ema_table: entry {i}: p and ema are the same memory')
+        rows_u.append((p.data_ptr(), ema.data_ptr(), n))
+        rows_s.append((p.data_ptr(), ema.data_ptr(), shadow.data_ptr() if shadow is not None else 0, n))
+        starts = torch.arange(0, n, EMA_CHUNK, dtype=torch.int64)
+        blocks.append(torch.stack([torch.full_like(starts, i), starts], 1))
+        keep += [p, ema] + ([shadow] if shadow is not None else [])
+        total += n
+        shadowed += n if shadow is not None else 0
+    blk = torch.cat(blocks).reshape(-1) if blocks else torch.zeros(0, dtype=torch.int64)
+
+    def table(rows, width):
+        head = torch.tensor(rows, dtype=torch.int64).reshape(-1) if rows else torch.zeros(0, dtype=torch.int64)
+        assert head.numel() == width * len(rows)
+        t = torch.cat([head, blk])
+        return (t if t.numel() else torch.zeros(1, dtype=torch.int64)).to(device)
+
+    return EmaTable(table(rows_u, 3), table(rows_s, 4), len(rows_u), blk.numel() // 2, total, shadowed, tuple(keep))
+
+
+def ema_update(table, momentum):
+    """ema = (1 - momentum) * ema + momentum * p over every entry of the table: one launch, fp32, on the current stream.
+    ``momentum`` is a launch argument: it may change every call at no cost."""
+    momentum = float(momentum)
+    if not 0.0 <= momentum <= 1.0:
+        raise ValueError(f'ema_update: momentum must lie in [0, 1], got {momentum}')
+    with _Timed('ema_update_kernel', 3 * table.numel, 12 * table.numel):
+        check(_lib.lib().clv_ema_update(_ptr(table.update), table.n_entries, table.n_blocks, momentum, _stream()),
+              'clv_ema_update')
+
+
+def ema_swap(table):
+    """Exchange p and ema of every entry in place, bit for bit, and rewrite the 16-bit copies of the new p: one launch."""
+    with _Timed('ema_swap_kernel', 0, 16 * table.numel + 2 * table.shadow_numel):
+        check(_lib.lib().clv_ema_swap(_ptr(table.swap), table.n_entries, table.n_blocks, _stream()), 'clv_ema_swap')
+
+
 # --------------------------------------------------------------------------- video QA / fill-in-the-blank (csrc/qa.hip)
 QA_MASK_ID = 103          # BERT [MASK]: the answer row of fill-in-the-blank (multimodal_transformer_finetune.py:100-102)
 

@@ -9,13 +9,16 @@
   its behaviour once the shorter loader is exhausted;
 * checkpoints in the reference's ``{'meta', 'state_dict', 'optimizer'}`` layout (``epoch_based_runner.py:25-58``);
 * ``EvalHook``: validation during training — schedule, rule inference and best-checkpoint keeping of
-  ``mmaction/core/hooks/my_eval_hook.py:404-880`` (``tools/train.py --validate``, ``tools/train.py:192-209``).
+  ``mmaction/core/hooks/my_eval_hook.py:404-880`` (``tools/train.py --validate``, ``tools/train.py:192-209``);
+* ``ExpMomentumEMAHook`` / ``LinearMomentumEMAHook``: the ``ema_hook`` of ``tools/train.py:212-220``
+  (``mmaction/core/hooks/ema.py``) — schedules and call points here, the average itself in ``CloverEngine``.
 
 The step itself is ``CloverEngine.step`` (or any object with ``train_step``); nothing here touches the GPU except the
 test loops ``EvalHook`` calls (``clover_amd.evaluation``).
 """
 import ast
 import copy
+import math
 import os
 import runpy
 import time
@@ -396,6 +399,8 @@ class EvalHook(Hook):
             return
         when = dict(epoch=runner.epoch + 1) if self.by_epoch else dict(iter=runner.iter + 1)
         rec = dict(when, mode='val', **{k: float(v) for k, v in eval_res.items()})
+        if getattr(runner.stepper, 'ema_names', None):           # an engine with a weight EMA: which weights were scored
+            rec['ema'] = bool(runner.stepper.ema_swapped)
         self.records.append(rec)
         if self.printer:
             self.printer(rec)
@@ -424,6 +429,94 @@ class EvalHook(Hook):
                          f'{float(key_score):0.4f} at {current.replace("_", " ")}')
 
 
+class BaseEMAHook(Hook):
+    """``ema_hook`` (mmaction/core/hooks/ema.py:8-97): evaluation, best-checkpoint selection and every saved checkpoint
+    use an exponential moving average of the weights, training goes on with the raw ones.
+
+    The average lives in the engine (``CloverEngine.ema_enable`` / ``ema_update`` / ``ema_swap``: fp32 slabs, one HIP launch
+    per update and per exchange) — this class is the schedule and the call points:
+
+    * ``before_run``: ``ema_enable(skip_buffers)``, which registers the ``ema_*`` buffers, THEN ``runner.resume(resume_from)``
+      if given, so that the checkpoint's ``ema_*`` entries find their buffers (:43-62);
+    * ``after_train_iter``: an update with ``momentum_fun(runner.iter)`` (or ``momentum``) when
+      ``(runner.iter + 1) % interval == 0`` — also after a step the loss scaler skipped, and once per loader step in the
+      multi-loader runner, whose steps of one batch index share ``runner.iter`` (:68-79);
+    * ``after_train_epoch`` / ``before_train_epoch``: exchange weights and average (:81-97).  The first epoch's exchange
+      swaps equal values; it is what makes a resumed run work: a checkpoint written at an epoch's end holds the average in
+      the parameters and the weights in ``ema_*``, and the first ``before_train_epoch`` after the resume puts them back.
+      ``engine.ema_swapped`` says which way round they are: True from ``before_run`` and from every epoch's end until the
+      next epoch begins (the engine refuses to train then), False during an epoch.
+
+    Registered with priority 49 (``tools/train.py:220``) it runs ahead of ``CheckpointHook`` and ``EvalHook``."""
+
+    def __init__(self, momentum=0.0002, interval=1, skip_buffers=False, resume_from=None, momentum_fun=None):
+        assert 0 < momentum < 1
+        self.momentum, self.interval, self.skip_buffers = momentum, interval, skip_buffers
+        self.checkpoint, self.momentum_fun = resume_from, momentum_fun
+
+    def before_run(self, runner):
+        eng = runner.stepper
+        missing = [a for a in ('ema_enable', 'ema_update', 'ema_swap') if not hasattr(eng, a)]
+        if missing:
+            raise TypeError(f'{type(self).__name__}: the weight EMA lives in the CloverEngine (its fp32 slabs and the 16-bit '
+                            f'copies the kernels compute from); the stepper {type(eng).__name__} has no '
+                            f'{", ".join(missing)} — drive the run with a CloverEngine')
+        eng.ema_enable(skip_buffers=self.skip_buffers)
+        if self.checkpoint is not None:
+            runner.resume(self.checkpoint)
+        # Until the first before_train_epoch the parameters COUNT as the average: after a resume they are it (see above),
+        # at a fresh start average and weights are equal, so the label costs nothing — and the exchange that opens every
+        # epoch, the first included, then leaves ``ema_swapped`` False while the engine trains.
+        eng.ema_swapped = True
+
+    def get_momentum(self, runner):
+        return self.momentum_fun(runner.iter) if self.momentum_fun else self.momentum
+
+    def after_train_iter(self, runner):
+        if (runner.iter + 1) % self.interval != 0:
+            return
+        runner.stepper.ema_update(self.get_momentum(runner))
+
+    def after_train_epoch(self, runner):
+        runner.stepper.ema_swap()              # the average goes in ahead of EvalHook / CheckpointHook
+
+    def before_train_epoch(self, runner):
+        runner.stepper.ema_swap()              # ... and out again (at the first epoch: equal values, see above)
+
+
+class ExpMomentumEMAHook(BaseEMAHook):
+    """:100-111 — the momentum decays from ~1 towards ``momentum`` with time constant ``total_iter``."""
+
+    def __init__(self, total_iter=2000, **kwargs):
+        super().__init__(**kwargs)
+        self.total_iter = total_iter
+        self.momentum_fun = lambda x: (1 - self.momentum) * math.exp(-(1 + x) / total_iter) + self.momentum
+
+
+class LinearMomentumEMAHook(BaseEMAHook):
+    """:114-125 — ``momentum ** interval``, capped by ``(1 + x) / (warm_up + x)`` during the first iterations."""
+
+    def __init__(self, warm_up=100, **kwargs):
+        super().__init__(**kwargs)
+        self.warm_up = warm_up
+        self.momentum_fun = lambda x: min(self.momentum ** self.interval, (1 + x) / (warm_up + x))
+
+
+EMA_HOOKS = {c.__name__: c for c in (BaseEMAHook, ExpMomentumEMAHook, LinearMomentumEMAHook)}
+
+# mmcv's named priorities (mmcv/runner/priority.py): a lower value runs first
+PRIORITIES = dict(HIGHEST=0, VERY_HIGH=10, HIGH=30, ABOVE_NORMAL=40, NORMAL=50, BELOW_NORMAL=60, LOW=70, VERY_LOW=90,
+                  LOWEST=100)
+
+
+def get_priority(priority):
+    if isinstance(priority, str):
+        return PRIORITIES[priority.upper()]
+    if not isinstance(priority, int) or not 0 <= priority <= 100:
+        raise ValueError(f'priority must be an integer in 0..100 or one of {sorted(PRIORITIES)}, got {priority!r}')
+    return priority
+
+
 class CloverRunner:
     """``stepper`` is a CloverEngine (``step(batch)``) or a module with ``train_step(batch, optimizer)``."""
 
@@ -437,8 +530,14 @@ class CloverRunner:
         self.hooks, self.outputs, self.mode = [], None, None
         self.epoch_len = None                 # len(runner.data_loader): the longest loader in multi-loader mode
 
-    def register_hook(self, hook):
-        self.hooks.append(hook)
+    def register_hook(self, hook, priority=50):
+        """mmcv's ``register_hook``: hooks run in the order of their priority (lower first; names as in mmcv), hooks of
+        equal priority in the order of their registration."""
+        hook.priority = get_priority(priority)
+        at = len(self.hooks)
+        while at > 0 and getattr(self.hooks[at - 1], 'priority', 50) > hook.priority:
+            at -= 1
+        self.hooks.insert(at, hook)
 
     def call_hook(self, name):
         for h in self.hooks:

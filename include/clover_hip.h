@@ -554,6 +554,26 @@ int clv_sumsq_ranges(const float* base, const void* table, int32_t n_blocks, flo
 int clv_adamw_step_dev(float* p, const float* g, float* m, float* v, void* shadow, const void* state, int64_t n,
                        float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ------------------------------------------------------------------ weight EMA (csrc/ema.hip)
+ * The reference's `ema_hook` (mmaction/core/hooks/ema.py:68-97: per tensor `buf.mul_(1 - m).add_(p, alpha=m)` every
+ * iteration, and a clone + two copies per tensor to exchange weights and averages around evaluation / checkpoints) as one
+ * launch per model each.  Both walk a device TABLE the caller builds once:
+ *     n_entries x entry, then n_blocks x {int64 entry index, int64 start}   (8-byte aligned, contiguous)
+ * with one block record per chunk of <= CLV_EMA_CHUNK floats of an entry (start = a multiple of CLV_EMA_CHUNK, < n); every
+ * element of every entry is covered by exactly one record.  A chunk whose pointers are 16-byte aligned is moved 16 bytes per
+ * lane; any other one element by element (tensors of any length and 4-byte alignment are legal).  No atomics.
+ *   clv_ema_update: entry = {const float* p; float* ema; int64 n}:  ema = (1 - m) * ema + m * p in fp32, with 1 - m formed
+ *     in double on the host and rounded to fp32 once.  m is a launch argument (0 <= m <= 1): it may change every call.
+ *   clv_ema_swap: entry = {float* p; float* ema; void* shadow; int64 n}: p and ema exchange their bit patterns in place
+ *     (every address stays valid: captured graphs keep reading p); shadow (bf16, may be NULL) receives the 16-bit copy of
+ *     the new p, rounded exactly as clv_adamw_step_dev rounds the one it writes. */
+#define CLV_EMA_CHUNK 4096
+#define CLV_EMA_UPDATE_ENTRY_BYTES 24
+#define CLV_EMA_SWAP_ENTRY_BYTES 32
+#define CLV_EMA_BLOCK_BYTES 16
+int clv_ema_update(const void* table, int32_t n_entries, int32_t n_blocks, double momentum, void* stream);
+int clv_ema_swap(const void* table, int32_t n_entries, int32_t n_blocks, void* stream);
+
 /* ------------------------------------------------------------------ parity mode (fp32 storage + fp32 arithmetic)
  * The reference's CPU path is fp32 (north_star: "match the reference mmaction CPU path ... losses within 1e-3").  The
  * training path above computes on bf16 MFMA operands; these two entry points let the SAME host graph (registered modules,

@@ -137,6 +137,18 @@ def main():
                                   candidates=st.get('candidates') if mc else None,
                                   captions=st.get('captions') if varied else None)
         runner.register_hook(EvalHook(val, printer=print if rank == 0 else None, **ev))
+    if cfg.get('ema_hook'):                              # tools/train.py:212-220 — on EVERY rank: each keeps its own average
+        from clover_amd.runner import EMA_HOOKS
+        ema_cfg = dict(cfg.ema_hook)
+        ema_type, priority = ema_cfg.pop('type'), ema_cfg.pop('priority', 49)
+        if ema_type not in EMA_HOOKS:
+            raise KeyError(f'ema_hook: type {ema_type!r} is not one of {sorted(EMA_HOOKS)}')
+        if args.resume_from:
+            # the checkpoint's ema_* entries (the raw weights, see BaseEMAHook) can only be loaded once the hook has
+            # registered their buffers: the hook resumes again from its before_run
+            ema_cfg.setdefault('resume_from', args.resume_from)
+        # priority 49: ahead of CheckpointHook and EvalHook in after_train_epoch, so both see the averaged weights
+        runner.register_hook(EMA_HOOKS[ema_type](**ema_cfg), priority=priority)
     if args.resume_from:
         runner.resume(args.resume_from)
     elif args.load_from:
