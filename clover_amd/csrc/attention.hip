@@ -50,10 +50,13 @@ struct Geom {
     // few (group, head) pairs (the fusion encoder: 16 x 12 = 192 on 256 CUs): tsplit workgroups per pair, each staging
     // the pair's K / V (or Q / dO) and taking every tsplit-th set of 4 query (key) tiles
     int tsplit;
-    // long sequences (mode 0, 448 < N <= 896 keys): the tokens STAGED in LDS — keys in the forward / dQ kernels, queries in
-    // the dK / dV kernel — are split into nparts contiguous parts of pt16 tokens, one workgroup set per part; each set
-    // writes its partial result (o + lse per key part, dq per key part, dk / dv per query part) to the caller's scratch
-    // and a combine kernel merges them (seq_combine_*).  nparts = 1: everything below degenerates to the plain kernels.
+    // long sequences (mode 0, 448 < N <= SEQ_MAX_KEYS = 4096 keys): the tokens STAGED in LDS — keys in the forward / dQ
+    // kernels, queries in the dK / dV kernel — are split into nparts = P = ceil(tiles / 28) <= SEQ_MAX_PARTS contiguous
+    // parts of pt16 = ceil(tiles / P) * 16 tokens, one workgroup set per part; each set walks ALL the looped tiles
+    // (tsplit = P workgroups of at most nkt >= pt16 / 16 tiles each) and writes its partial result (o + lse per key part,
+    // dq per key part, dk / dv per query part) to the caller's scratch as [part][...]; a combine kernel merges the P
+    // partial results (seq_combine_*).  The last part may be shorter; the pad keys of EVERY part's last tile(s) carry
+    // -inf.  nparts = 1: everything below degenerates to the plain kernels.
     int grp0;                            // first group of this launch (the table-gradient path runs the dQ kernel in chunks)
     int nparts, pt16;
     int lddq, lddk, lddv;                // row strides of the dq / dk / dv OUTPUTS (= ldq / ldk / ldv unless partial)
@@ -1555,19 +1558,18 @@ __global__ void __launch_bounds__(256) seq_combine_fwd_kernel(const bf16_t* __re
     const int c = (int)(idx - row * cpr) * 8, h = c / HD;
     const int64_t grp = row / G.g.N, n = row - grp * G.g.N;
     const int64_t li = (grp * G.g.nH + h) * G.g.N + n;
-    float lp[4], m = -INFINITY;
-    for (int p = 0; p < G.nparts; ++p) {
-        lp[p] = lse_part[p * G.lse_ps + li];
-        m = fmaxf(m, lp[p]);
-    }
+    // the parts' lse values (up to SEQ_MAX_PARTS of them) are read once per pass instead of kept in a private array
+    const float* lp = lse_part + li;
+    float m = -INFINITY;
+    for (int p = 0; p < G.nparts; ++p) m = fmaxf(m, lp[p * G.lse_ps]);
     float tot = 0.f;
-    for (int p = 0; p < G.nparts; ++p) tot += __expf(lp[p] - m);
+    for (int p = 0; p < G.nparts; ++p) tot += __expf(lp[p * G.lse_ps] - m);
     const float L = m + __logf(tot);
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     for (int p = 0; p < G.nparts; ++p) {
-        const float w = __expf(lp[p] - L);
+        const float w = __expf(lp[p * G.lse_ps] - L);
         Frag8 f;
         f.u4 = *reinterpret_cast<const uint4*>(o_part + p * G.o_ps + row * C + c);
 #pragma unroll
@@ -1604,6 +1606,8 @@ __global__ void __launch_bounds__(256) seq_combine_bwd_kernel(const bf16_t* __re
 
 // ------------------------------------------------------------------------- host side
 constexpr int SEQ_ONE_PART_TILES = 28;       // 448 keys: the largest instantiation (LDS)
+constexpr int SEQ_MAX_KEYS = 4096;           // the bound of clv_attn_probs_mean as well: the QA attention map covers the same range
+constexpr int SEQ_MAX_PARTS = (SEQ_MAX_KEYS / 16 + SEQ_ONE_PART_TILES - 1) / SEQ_ONE_PART_TILES;   // 10
 bool make_geom(const ClvAttnGeom* g, Geom& G) {
     if (!g) return false;
     G.g = *g;
@@ -1628,12 +1632,17 @@ bool make_geom(const ClvAttnGeom* g, Geom& G) {
         G.pt16 = tiles * 16;
         G.lddq = g->ldq; G.lddk = g->ldk; G.lddv = g->ldv;
         G.o_ps = G.lse_ps = G.dq_ps = G.dk_ps = G.dv_ps = 0;
-        // K / V (Q / dO) of one (sample, head) exceed the LDS: two parts (beyond two parts' reach the bf16 launchers find
-        // no instantiation and report CLV_ERR_UNSUPPORTED; the fp32 parity kernel stages nothing and takes any length)
-        if (g->mode == 0 && tiles > SEQ_ONE_PART_TILES && tiles <= 2 * SEQ_ONE_PART_TILES) {
-            G.nparts = 2;
-            G.pt16 = (tiles + 1) / 2 * 16;
-            G.tsplit = 2;                                   // looped tiles per workgroup set: <= 64 (see launch checks)
+        // K / V (Q / dO) of one (sample, head) exceed the LDS: P parts of at most 28 tiles (beyond SEQ_MAX_KEYS the 16-bit
+        // launchers find no instantiation and report CLV_ERR_UNSUPPORTED; the fp32 parity kernel stages nothing and takes
+        // any length)
+        if (g->mode == 0 && tiles > SEQ_ONE_PART_TILES && g->N <= SEQ_MAX_KEYS) {
+            G.nparts = (tiles + SEQ_ONE_PART_TILES - 1) / SEQ_ONE_PART_TILES;
+            G.pt16 = (tiles + G.nparts - 1) / G.nparts * 16;
+            // P workgroups of a (group, head, part) set share the looped tiles: each takes at most nkt >= pt16 / 16 of
+            // them, so P * roundup(nkt, waves) >= tiles (the launch checks)
+            G.tsplit = G.nparts;
+            static_assert(SEQ_MAX_PARTS * SEQ_ONE_PART_TILES * 16 >= SEQ_MAX_KEYS, "parts cover the longest sequence");
+            if ((G.nparts - 1) * G.pt16 >= g->N) return false;   // every part stages at least one token
             const int64_t tokens = (int64_t)g->groups * g->N, C = (int64_t)g->nH * g->hd;
             G.o_ps = tokens * C;
             G.lse_ps = (int64_t)g->groups * g->nH * g->N;
@@ -1736,7 +1745,7 @@ int launch_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                  (const bf16_t*)v, (bf16_t*)o, lse, bias, rid, kmask, seed, G));
         return clv_check_launch();
     }
-    // two key parts: partial o (dense [tokens][C]) + lse per part into the scratch, then the merge
+    // several key parts: partial o (dense [tokens][C]) + lse per part into the scratch, then the merge
     if (!G.g.work || (NKT + WAVES - 1) / WAVES * WAVES * G.tsplit < (G.g.N + 15) / 16) return CLV_ERR_UNSUPPORTED;
     Geom P = G;
     P.g.ldo = G.g.nH * G.g.hd;
@@ -1956,7 +1965,13 @@ extern "C" int64_t clv_attn_seq_work_bytes(const ClvAttnGeom* geom) {
     return fwd > bwd ? fwd : bwd;
 }
 
-extern "C" int clv_attn_seq_max_keys(void) { return 2 * SEQ_ONE_PART_TILES * 16; }
+extern "C" int clv_attn_seq_max_keys(void) { return SEQ_MAX_KEYS; }
+
+extern "C" int clv_attn_seq_parts(const ClvAttnGeom* geom) {
+    Geom G;
+    if (!make_geom(geom, G) || pick_nkt(G.nparts > 1 ? G.pt16 : G.g.N) < 0) return 0;
+    return G.nparts;
+}
 
 extern "C" int64_t clv_attn_dbias_index_count(const ClvAttnGeom* geom) {
     Geom G;

@@ -7,7 +7,9 @@
 //
 // One wave per row, the row held in registers (<= 2048 keys): lane l owns keys l, l+64, ... so every load / store
 // instruction of a wave covers 128 contiguous bytes.  HBM-bound: fwd reads 2 B and writes 2 (+2 with dropout) B per
-// score, bwd reads 4 and writes 2.
+// score, bwd reads 4 and writes 2.  Longer rows (the fused kernels take sequences up to 4096 keys, so this path starts
+// beyond that) are walked from memory instead: the *_stream_kernel variants read a row once per pass (maximum, sum,
+// write; dot product, write) — the second and third pass find it in the cache.
 #include "common.hpp"
 #include "../../include/clover_hip.h"
 
@@ -85,6 +87,52 @@ softmax_rows_bwd_kernel(const bf16_t* __restrict__ p, const bf16_t* __restrict__
     }
 }
 
+// ---- rows beyond the register-resident forms: the same arithmetic, the row re-read per pass
+template <bool DROP>
+__global__ void __launch_bounds__(SM_WAVES * 64)
+softmax_rows_fwd_stream_kernel(const bf16_t* __restrict__ scores, const float* __restrict__ kmask, bf16_t* __restrict__ p,
+                               bf16_t* __restrict__ pd, const unsigned long long* __restrict__ seed, int64_t rows, int S,
+                               int ld, int rows_per_group, float scale_log2e, unsigned thresh, float inv_keep) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * SM_WAVES + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const bf16_t* src = scores + row * ld;
+    const float* km = kmask ? kmask + (row / rows_per_group) * S : nullptr;
+    auto score = [&](int j) { return bf2f(src[j]) * scale_log2e + (km ? km[j] * 1.4426950408889634f : 0.f); };
+    float m = -INFINITY;
+    for (int j = lane; j < S; j += 64) m = fmaxf(m, score(j));
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < S; j += 64) sum += __builtin_amdgcn_exp2f(score(j) - m);
+    const float inv = 1.0f / wave_sum(sum);
+    const unsigned long long sd = DROP ? seed[0] : 0ull;
+    for (int j = lane; j < S; j += 64) {
+        const float v = __builtin_amdgcn_exp2f(score(j) - m) * inv;
+        p[row * ld + j] = f2bf(v);
+        if (DROP) pd[row * ld + j] = f2bf(v * keep_scale(sd, (unsigned)row, (unsigned)j, thresh, inv_keep));
+    }
+}
+
+// (ds may alias dpd: every element is read and then written by the one lane that owns it)
+template <bool DROP>
+__global__ void __launch_bounds__(SM_WAVES * 64)
+softmax_rows_bwd_stream_kernel(const bf16_t* __restrict__ p, const bf16_t* dpd, bf16_t* ds,
+                               const unsigned long long* __restrict__ seed, int64_t rows, int S, int ld, float scale,
+                               unsigned thresh, float inv_keep) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * SM_WAVES + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const unsigned long long sd = DROP ? seed[0] : 0ull;
+    auto dprob = [&](int j) {
+        const float d = bf2f(dpd[row * ld + j]);
+        return DROP ? d * keep_scale(sd, (unsigned)row, (unsigned)j, thresh, inv_keep) : d;
+    };
+    float dot = 0.f;
+    for (int j = lane; j < S; j += 64) dot += bf2f(p[row * ld + j]) * dprob(j);
+    dot = wave_sum(dot);
+    for (int j = lane; j < S; j += 64) ds[row * ld + j] = f2bf(bf2f(p[row * ld + j]) * (dprob(j) - dot) * scale);
+}
+
 int pick_iters(int S) {
     const int need = (S + 63) / 64;
     const int opts[] = {4, 8, 13, 16, 32};
@@ -110,7 +158,6 @@ extern "C" int clv_softmax_rows_fwd(const void* scores, const float* kmask, void
         return CLV_ERR_ARG;
     if (dropout_p > 0.f && (!pd || !seed)) return CLV_ERR_ARG;
     const int iters = pick_iters(S);
-    if (iters < 0) return CLV_ERR_UNSUPPORTED;
     if (rows > (int64_t)0xffffffffu) return CLV_ERR_UNSUPPORTED;          // the mask hash takes a 32-bit row id
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((rows + SM_WAVES - 1) / SM_WAVES));
@@ -119,7 +166,14 @@ extern "C" int clv_softmax_rows_fwd(const void* scores, const float* kmask, void
     const float inv_keep = 1.0f / (1.0f - dropout_p);
     const bf16_t* sc = (const bf16_t*)scores;
     const unsigned long long* sp = (const unsigned long long*)seed;
-    if (thresh) {
+    if (iters < 0) {                                                      // more than 2048 keys: the row is walked from memory
+        if (thresh)
+            hipLaunchKernelGGL((softmax_rows_fwd_stream_kernel<true>), grid, dim3(SM_WAVES * 64), 0, st, sc, kmask, (bf16_t*)p,
+                               (bf16_t*)pd, sp, rows, (int)S, (int)ld, (int)rows_per_group, sl, thresh, inv_keep);
+        else
+            hipLaunchKernelGGL((softmax_rows_fwd_stream_kernel<false>), grid, dim3(SM_WAVES * 64), 0, st, sc, kmask, (bf16_t*)p,
+                               (bf16_t*)pd, sp, rows, (int)S, (int)ld, (int)rows_per_group, sl, thresh, inv_keep);
+    } else if (thresh) {
         SM_DISPATCH(softmax_rows_fwd_kernel, true, sc, kmask, (bf16_t*)p, (bf16_t*)pd, sp, rows, (int)S, (int)ld,
                     (int)rows_per_group, sl, thresh, inv_keep)
     } else {
@@ -134,14 +188,20 @@ extern "C" int clv_softmax_rows_bwd(const void* p, const void* dpd, void* ds, co
     if (!p || !dpd || !ds || rows <= 0 || S <= 0 || ld < S || dropout_p < 0.f || dropout_p >= 1.f) return CLV_ERR_ARG;
     if (dropout_p > 0.f && !seed) return CLV_ERR_ARG;
     const int iters = pick_iters(S);
-    if (iters < 0) return CLV_ERR_UNSUPPORTED;
     if (rows > (int64_t)0xffffffffu) return CLV_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((rows + SM_WAVES - 1) / SM_WAVES));
     const unsigned thresh = (unsigned)((double)dropout_p * 4294967296.0);
     const float inv_keep = 1.0f / (1.0f - dropout_p);
     const unsigned long long* sp = (const unsigned long long*)seed;
-    if (thresh) {
+    if (iters < 0) {
+        if (thresh)
+            hipLaunchKernelGGL((softmax_rows_bwd_stream_kernel<true>), grid, dim3(SM_WAVES * 64), 0, st, (const bf16_t*)p,
+                               (const bf16_t*)dpd, (bf16_t*)ds, sp, rows, (int)S, (int)ld, scale, thresh, inv_keep);
+        else
+            hipLaunchKernelGGL((softmax_rows_bwd_stream_kernel<false>), grid, dim3(SM_WAVES * 64), 0, st, (const bf16_t*)p,
+                               (const bf16_t*)dpd, (bf16_t*)ds, sp, rows, (int)S, (int)ld, scale, thresh, inv_keep);
+    } else if (thresh) {
         SM_DISPATCH(softmax_rows_bwd_kernel, true, (const bf16_t*)p, (const bf16_t*)dpd, (bf16_t*)ds, sp, rows, (int)S,
                     (int)ld, scale, thresh, inv_keep)
     } else {

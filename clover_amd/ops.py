@@ -36,8 +36,8 @@ LIBRARY_GEMM_CALLS = {}     # {(site, shape): calls} of every GEMM that left the
 
 def _library_gemm(site, shape):
     """Every GEMM of the Clover configs runs on the own kernels, and no switch routes one elsewhere; only a shape they do
-    not take (a contraction that is not a multiple of 64 such as the 48-wide tiny model, a sequence beyond 896 keys, ...)
-    goes to the ROCm library, and only THROUGH HERE: counted in
+    not take (a contraction that is not a multiple of 64 such as the 48-wide tiny model, a sequence beyond
+    clv_attn_seq_max_keys() = 4096 keys, ...) goes to the ROCm library, and only THROUGH HERE: counted in
     LIBRARY_GEMM_CALLS (bench.py prints the table, the step tests assert it stays empty), announced once per shape, and
     refused with CLOVER_STRICT_OWN_GEMM=1 — never silent."""
     key = (site, tuple(int(v) for v in shape))
@@ -160,8 +160,9 @@ def _dbias_index(g, device):
 def _kname(kernel, g):
     """Device-kernel name as rocprofv3 prints it: template <HD, NKT, DROP, MODE> (attention.hip CLV_PICK)."""
     need = (g.N + 15) // 16
-    if g.mode == 0 and need > 28:             # a long sequence runs as two parts of staged tokens (attention.hip make_geom)
-        need = (need + 1) // 2
+    if g.mode == 0 and need > 28:             # a long sequence runs as P parts of staged tokens (attention.hip make_geom):
+        parts = (need + 27) // 28             # the instantiation is chosen from the PART's tiles, not from N
+        need = (need + parts - 1) // parts
     nkt = next((o for o in (2, 8, 13, 14, 15, 16, 25, 28) if o >= need), need)       # > 28: the C call reports UNSUPPORTED
     drop = 'true' if (g.dropout_p > 0 and g.mode == 0) else 'false'
     if kernel == 'attn_bwd_dkv_kernel':
@@ -172,7 +173,9 @@ def _kname(kernel, g):
 def _attn_work(g, backward):
     """Algorithmic work of one attention call: 2 flops/MAC over the
     N x N x hd products (2 matmuls forward, 5 backward); bytes = q,k,v read + o written
-    (forward) or q,k,v,o,do read + dq,dk,dv written (backward), bf16."""
+    (forward) or q,k,v,o,do read + dq,dk,dv written (backward), bf16.  A sequence run as P parts does the same N x N
+    products (every part set walks all looped tiles against its own part of the staged ones); the P-fold re-staging and
+    the partial results in the scratch are the implementation's traffic, not counted here."""
     per = g.groups * g.nH * g.N * g.N * g.hd
     flops = (10 if backward else 4) * per
     tok = g.groups * g.N * g.nH * g.hd * 2
@@ -1730,7 +1733,7 @@ class _Attention(torch.autograd.Function):
             tab = _c(table.detach().float())
         o = torch.empty(qkv.shape[:-1] + (Cdim,), device=qkv.device, dtype=BF16)
         lse = torch.empty(g.groups * g.nH * g.N, device=qkv.device, dtype=torch.float32)
-        wbytes = _lib.lib().clv_attn_seq_work_bytes(C.byref(g))        # > 0: a sequence beyond the LDS, run as two parts
+        wbytes = _lib.lib().clv_attn_seq_work_bytes(C.byref(g))        # > 0: a sequence beyond the LDS, run as several parts
         seq_work = torch.empty(wbytes, device=qkv.device, dtype=torch.uint8) if wbytes > 0 else None
         g.work = seq_work.data_ptr() if seq_work is not None else None
         base = qkv.data_ptr()
@@ -1887,13 +1890,15 @@ def next_dropout_seed(device):
     return seed
 
 
-SEQ_FUSED_MAX_KEYS = 896          # fused kernels: up to 448 keys staged at once, longer sequences as two parts
-                                  # (clv_attn_seq_max_keys(); the 32-frame fusion sequence has 816 tokens)
+# fused kernels: up to 448 keys staged at once, longer sequences as ceil(tiles / 28) parts + a merge, up to 4096 keys (the
+# 32-frame fusion sequence has 816 tokens, the 64-frame one 1600).  Read at call time: a test sets it back to 896 to get the
+# unfused path below for comparison.
+SEQ_FUSED_MAX_KEYS = _lib.lib().clv_attn_seq_max_keys()
 
 
 class _LongSeqAttention(torch.autograd.Function):
-    """Self-attention for sequences beyond the fused kernels' LDS budget: batched library GEMMs for Q.K^T / P.V and
-    their gradients, the HIP row-softmax kernels (mask + softmax + dropout, and the backward) between them."""
+    """Self-attention for sequences beyond the fused kernels' reach (SEQ_FUSED_MAX_KEYS): batched library GEMMs for
+    Q.K^T / P.V and their gradients, the HIP row-softmax kernels (mask + softmax + dropout, and the backward) between them."""
 
     @staticmethod
     def forward(ctx, qkv, kmask, num_heads, dropout_p, seed):
@@ -1939,8 +1944,8 @@ class _LongSeqAttention(torch.autograd.Function):
 def seq_attention(qkv, kmask, num_heads, dropout_p=0.0):
     """BERT self-attention. qkv bf16 [B,S,3H]; kmask fp32 [B,S] additive ((1-m)*-10000) or None;
     dropout_p: dropout on the attention probabilities (HF attention_probs_dropout_prob).
-    Up to 896 tokens: the fused LDS-resident kernels (beyond 448 as two parts + a merge); longer sequences: the unfused
-    GEMM + row-softmax path."""
+    Up to SEQ_FUSED_MAX_KEYS (4096) tokens: the fused LDS-resident kernels (beyond 448 as parts of at most 448 staged
+    tokens + a merge); longer sequences: the unfused library GEMM + row-softmax path (counted, refused in strict mode)."""
     B, S, C3 = qkv.shape
     hd = C3 // 3 // num_heads
     if parity.enabled():

@@ -74,11 +74,12 @@ typedef struct ClvAttnGeom {
     float dropout_p;        /* dropout on the attention probabilities (HF attention_probs_dropout_prob), 0 = off */
     const int32_t* dbias_index; /* backward, optional: the device table clv_attn_dbias_index() built for this window
                                    geometry (N, bwd, bwh, bww) — the table-gradient gather then does no index arithmetic */
-    void* work;                 /* mode 0 with 448 < N <= clv_attn_seq_max_keys() (the 32-frame fusion sequence, 816 tokens,
-                                   cross_transformer.py:89-110): clv_attn_seq_work_bytes() of scratch.  K / V (Q / dO) of one
-                                   (sample, head) then exceed the LDS, so the staged tokens are split in two parts, each
-                                   with its own workgroups; the parts' results (o + lse; dq; dk / dv) meet in a merge
-                                   kernel.
+    void* work;                 /* mode 0 with 448 < N <= clv_attn_seq_max_keys() = 4096 (the 32-frame fusion sequence, 816
+                                   tokens, cross_transformer.py:89-110; the 64-frame one, 1600): clv_attn_seq_work_bytes() of
+                                   scratch.  K / V (Q / dO) of one (sample, head) then exceed the LDS, so the staged tokens are
+                                   split in P = clv_attn_seq_parts() = ceil(ceil(N / 16) / 28) <= 10 parts, each with its own
+                                   workgroups; the parts' results ([part][o] + [part][lse] forward, [part][dq | dk | dv]
+                                   [tokens][C] backward) meet in a merge kernel.
                                    mode 1, backward with a bias table, optional: clv_attn_dbias_partial_bytes() of 16-byte
                                    aligned memory that receives the slices' fp32 partial sums of the table gradient INSTEAD
                                    of the tail of clv_attn_bwd's `work` — a caller that gathers later (stage bit 8 +
@@ -92,6 +93,9 @@ typedef struct ClvAttnGeom {
  * (seed, group, head, query, key), so the backward regenerates it from the same seed. */
 int64_t clv_attn_seq_work_bytes(const ClvAttnGeom* geom);
 int clv_attn_seq_max_keys(void);
+/* The number of parts the staged tokens of this geometry are split in: 1 = not split (no scratch needed), 0 = the 16-bit
+ * kernels do not take the geometry (clv_attn_fwd / clv_attn_bwd report an error). */
+int clv_attn_seq_parts(const ClvAttnGeom* geom);
 int clv_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                  const float* bias, const int32_t* rid, const float* kmask, const void* seed,
                  const ClvAttnGeom* geom_host, void* stream);
@@ -137,7 +141,8 @@ int clv_attn_dbias_gather_batch(const ClvDbiasGather* entries, int32_t n, void* 
  * batched library GEMMs; these two kernels are what sits between them (HF BertSelfAttention, transformers 4.6.1
  * modeling_bert.py, reached through cross_transformer.py:95-108): one wave per row.
  * fwd: p[r][j] = softmax_j(scores[r][j]*scale + kmask[r / rows_per_group][j]); pd = p * keep/(1-p_drop) with the
- *      same counter-based mask as clv_attn_* (row id r, key j).  scores/p/pd bf16 [rows][ld], S <= 2048 keys;
+ *      same counter-based mask as clv_attn_* (row id r, key j).  scores/p/pd bf16 [rows][ld]; a row of up to 2048 keys is
+ *      held in registers, a longer one is walked from memory once per pass.
  *      kmask float [groups][S] or NULL; pd / seed may be NULL when dropout_p == 0.
  * bwd: ds = p * (dp - sum_j p_j dp_j) * scale with dp = dpd * keep/(1-p_drop); ds may alias dpd. */
 int clv_softmax_rows_fwd(const void* scores, const float* kmask, void* p, void* pd, const void* seed, int64_t rows,
