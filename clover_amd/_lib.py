@@ -195,6 +195,11 @@ SIGNATURES = {
     'clv_attn_probs_mean': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f, _p]),
     'clv_qa_choice_assemble': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
     'clv_qa_choice_assemble_bwd': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
+    'clv_qa_head_f32_fwd': (C.c_int, [_p] * 9 + [_f, _f] + [_p] * 5 + [_i32] * 4 + [_p]),
+    'clv_qa_head_f32_bwd': (C.c_int, [_p] * 14 + [_f] + [_p] * 9 + [_i32] * 4 + [_p]),
+    'clv_attn_probs_mean_f32': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f, _p]),
+    'clv_qa_choice_assemble_f32': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
+    'clv_qa_choice_assemble_f32_bwd': (C.c_int, [_p, _p, _p] + [_i32] * 5 + [_p]),
     'clv_retrieval_work_bytes': (C.c_int64, [_i64, _i64, _i32, _i32]),
     'clv_retrieval_rank': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _i32, _p]),
     'clv_retrieval_group_work_bytes': (C.c_int64, [_i64, _i64, _i32]),

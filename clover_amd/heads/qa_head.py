@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..builder import HEADS
+from ..nn import to_bf16
 
 
 def init_qa_weights(module):
@@ -32,7 +33,7 @@ class _FusedQAHead(nn.Module):
         if rows is None:                       # plain [..., D] rows (the reference's call: qa_head(itm_output))
             x = x.reshape(-1, 1, x.shape[-1])
             rows = torch.arange(x.shape[0], device=x.device, dtype=torch.int32)
-        x = x if x.dtype == ops.BF16 else x.to(ops.BF16)
+        x = to_bf16(x)                         # the path's storage type: fp32 in parity mode
         return ops.qa_head(x, rows, fc1.weight, fc1.bias, ln.weight, ln.bias, fc2.weight, fc2.bias,
                            drop_p=drop.p if self.training else 0.0, eps=ln.eps, labels=labels, num_choices=num_choices)
 

@@ -2631,6 +2631,26 @@ def qa_answer_rows(token_ids, seq_len, base, answer_mask, mask_id=QA_MASK_ID):
     return out[0], out[1]
 
 
+_QA_F32 = {'clv_qa_head_fwd': 'clv_qa_head_f32_fwd', 'clv_qa_head_bwd': 'clv_qa_head_f32_bwd',
+           'clv_attn_probs_mean': 'clv_attn_probs_mean_f32', 'clv_qa_choice_assemble': 'clv_qa_choice_assemble_f32',
+           'clv_qa_choice_assemble_bwd': 'clv_qa_choice_assemble_f32_bwd'}
+
+
+def _qa_entry(name, t, what):
+    """(function, its name) of the QA entry point for activation ``t``: ``name`` on 16-bit storage outside parity mode,
+    its fp32-storage instantiation (_QA_F32) on fp32 storage inside it.  A mismatch raises: a 16-bit
+    activation inside parity mode means a producer rounded where it should not have, and an fp32 one outside it that a
+    producer left the 16-bit path.  None of these ops is a rounding source of parity.ROUND_KINDS, so there is nothing to
+    re-inject (parity.rnd) here: the head's logits are fp32 on the 16-bit path too, choice assembly is a copy, and the
+    attention map is computed in fp32 from the stored q / k."""
+    want = torch.float32 if parity.enabled() else BF16
+    if t.dtype != want:
+        where = 'in fp32 parity mode (CLOVER_PARITY)' if parity.enabled() else 'on the 16-bit path'
+        raise NotImplementedError(f'{what} takes {want} activations {where}, got {t.dtype}')
+    name = _QA_F32[name] if parity.enabled() else name
+    return getattr(_lib.lib(), name), name
+
+
 def _qa_grad_out(p):
     """(fp32 buffer the head's backward ADDS the gradient of p into, whether it is the engine's slab sink)."""
     sink = getattr(p, '_clv_grad', None)
@@ -2649,10 +2669,8 @@ class _QAHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, rows, w1, b1, gamma, beta, w2, b2, seed, drop_p, eps, labels, C):
         _need_gpu(h, rows)
-        if parity.enabled():
-            raise NotImplementedError('the QA head has no fp32 parity-mode kernels (CLOVER_PARITY): run it on the 16-bit '
-                                      'path')
-        assert h.dtype == BF16, h.dtype
+        fwd, fwd_name = _qa_entry('clv_qa_head_fwd', h, 'the QA head')
+        ctx.bwd = _qa_entry('clv_qa_head_bwd', h, 'the QA head')
         h = _c(h)
         D = h.shape[-1]
         H, K = w1.shape[0], w2.shape[0]
@@ -2665,9 +2683,8 @@ class _QAHead(torch.autograd.Function):
         stats = torch.empty(2, M, device=dev, dtype=torch.float32)
         logits = torch.empty(M, K, device=dev, dtype=torch.float32)
         L = _lib.lib()
-        check(L.clv_qa_head_fwd(_ptr(h), _ptr(rows), *[_ptr(t) for t in ws], _ptr(seed), float(drop_p), float(eps),
-                                _ptr(zg[0]), _ptr(zg[1]), _ptr(stats[0]), _ptr(stats[1]), _ptr(logits), M, D, H, K,
-                                _stream()), 'clv_qa_head_fwd')
+        check(fwd(_ptr(h), _ptr(rows), *[_ptr(t) for t in ws], _ptr(seed), float(drop_p), float(eps), _ptr(zg[0]),
+                  _ptr(zg[1]), _ptr(stats[0]), _ptr(stats[1]), _ptr(logits), M, D, H, K, _stream()), fwd_name)
         ctx.cfg = (h.shape, M, D, H, K, float(drop_p))
         ctx.params = (w1, b1, gamma, beta, w2, b2)
         if labels is None:
@@ -2698,10 +2715,10 @@ class _QAHead(torch.autograd.Function):
         dh = torch.zeros(shape, device=dev, dtype=h.dtype)
         scratch = torch.empty(2, M, H, device=dev, dtype=torch.float32)
         outs = [_qa_grad_out(p) for p in ctx.params]
-        check(_lib.lib().clv_qa_head_bwd(_ptr(h), _ptr(rows), _ptr(w1), _ptr(gamma), _ptr(beta), _ptr(w2), _ptr(zg[0]),
-                                         _ptr(zg[1]), _ptr(stats[0]), _ptr(stats[1]), _ptr(dl), _ptr(s1), _ptr(s2),
-                                         _ptr(seed), drop_p, _ptr(scratch[0]), _ptr(scratch[1]), _ptr(dh),
-                                         *[_ptr(t) for t, _ in outs], M, D, H, K, _stream()), 'clv_qa_head_bwd')
+        bwd, bwd_name = ctx.bwd
+        check(bwd(_ptr(h), _ptr(rows), _ptr(w1), _ptr(gamma), _ptr(beta), _ptr(w2), _ptr(zg[0]), _ptr(zg[1]),
+                  _ptr(stats[0]), _ptr(stats[1]), _ptr(dl), _ptr(s1), _ptr(s2), _ptr(seed), drop_p, _ptr(scratch[0]),
+                  _ptr(scratch[1]), _ptr(dh), *[_ptr(t) for t, _ in outs], M, D, H, K, _stream()), bwd_name)
         grads = []
         for p, (t, is_sink) in zip(ctx.params, outs):
             if is_sink:
@@ -2713,8 +2730,9 @@ class _QAHead(torch.autograd.Function):
 
 
 def qa_head(h, rows, w1, b1, gamma, beta, w2, b2, drop_p=0.0, eps=1e-5, labels=None, num_choices=None):
-    """h [N, S, D] 16-bit (e.g. the fusion output), rows int32 [M] into h viewed as [N * S, D] -> logits fp32 [M, K]; with
-    ``labels`` (multiple choice, K = 1): the CrossEntropyLoss of the logits viewed [M / num_choices, num_choices]."""
+    """h [N, S, D] 16-bit (fp32 in parity mode: the same kernels in fp32 storage, d h returned in fp32), e.g. the fusion
+    output, rows int32 [M] into h viewed as [N * S, D] -> logits fp32 [M, K]; with ``labels`` (multiple choice, K = 1): the
+    CrossEntropyLoss of the logits viewed [M / num_choices, num_choices]."""
     seed = next_dropout_seed(h.device) if drop_p > 0 else None
     if labels is not None:
         assert w2.shape[0] == 1 and num_choices and rows.numel() % num_choices == 0
@@ -2723,44 +2741,47 @@ def qa_head(h, rows, w1, b1, gamma, beta, w2, b2, drop_p=0.0, eps=1e-5, labels=N
 
 
 def choice_assemble(visual, text, C):
-    """visual 16-bit [B, n_vis, D], text [B*C, L, D] -> the multiple-choice fusion input [B*C, n_vis + L, D] (one launch)."""
+    """visual 16-bit [B, n_vis, D] (fp32 in parity mode), text [B*C, L, D] -> the multiple-choice fusion input
+    [B*C, n_vis + L, D] (one launch)."""
     _need_gpu(visual, text)
-    if visual.dtype != BF16 or text.dtype != BF16:
-        raise TypeError(f'choice_assemble takes {BF16} rows, got {visual.dtype} / {text.dtype}')
+    if visual.dtype != text.dtype:
+        raise TypeError(f'choice_assemble takes rows of one type, got {visual.dtype} / {text.dtype}')
+    try:
+        fn, name = _qa_entry('clv_qa_choice_assemble', visual, 'choice_assemble')
+    except NotImplementedError as e:
+        raise TypeError(str(e)) from None
     visual, text = _c(visual), _c(text)
     B, n_vis, D = visual.shape
     BC, L, _ = text.shape
     assert BC == B * C and text.shape[2] == D, (visual.shape, text.shape, C)
     feat = torch.empty(BC, n_vis + L, D, device=visual.device, dtype=visual.dtype)
-    check(_lib.lib().clv_qa_choice_assemble(_ptr(visual), _ptr(text), _ptr(feat), B, int(C), n_vis, L, D, _stream()),
-          'clv_qa_choice_assemble')
+    check(fn(_ptr(visual), _ptr(text), _ptr(feat), B, int(C), n_vis, L, D, _stream()), name)
     return feat
 
 
 def choice_assemble_bwd(dfeat, cfg):
     """-> (d visual [B, n_vis, D]: the sum over the C candidates, d text [B*C, L, D]) (one launch)."""
     B, C, n_vis, L, D = cfg
-    d = _c(dfeat.to(BF16))
+    d = _c(dfeat.to(torch.float32 if parity.enabled() else BF16))
+    fn, name = _qa_entry('clv_qa_choice_assemble_bwd', d, 'choice_assemble_bwd')
     dv = torch.empty(B, n_vis, D, device=d.device, dtype=d.dtype)
     dt = torch.empty(B * C, L, D, device=d.device, dtype=d.dtype)
-    check(_lib.lib().clv_qa_choice_assemble_bwd(_ptr(d), _ptr(dv), _ptr(dt), B, C, n_vis, L, D, _stream()),
-          'clv_qa_choice_assemble_bwd')
+    check(fn(_ptr(d), _ptr(dv), _ptr(dt), B, C, n_vis, L, D, _stream()), name)
     return dv, dt
 
 
 def attn_probs_mean(qkv, kmask, num_heads):
-    """forward_test's attention map: qkv 16-bit [N, S, 3 C] of a BERT layer, kmask fp32 additive [N, S] (or None) ->
-    fp32 [N, S, S] = softmax(q k^T / sqrt(hd) + kmask) averaged over the heads (inference only: no autograd)."""
+    """forward_test's attention map: qkv 16-bit (fp32 in parity mode) [N, S, 3 C] of a BERT layer, kmask fp32 additive
+    [N, S] (or None) -> fp32 [N, S, S] = softmax(q k^T / sqrt(hd) + kmask) averaged over the heads (inference only: no
+    autograd)."""
     _need_gpu(qkv)
-    if parity.enabled() or qkv.dtype != BF16:
-        raise NotImplementedError(f'attn_probs_mean reads 16-bit qkv (got {qkv.dtype}); no fp32 parity-mode kernel')
+    fn, name = _qa_entry('clv_attn_probs_mean', qkv, 'attn_probs_mean')
     qkv = _c(qkv.detach())
     N, S, C3 = qkv.shape
     hd = C3 // 3 // num_heads
     out = torch.empty(N, S, S, device=qkv.device, dtype=torch.float32)
     km = _c(kmask.detach().float()) if kmask is not None else None
-    check(_lib.lib().clv_attn_probs_mean(_ptr(qkv), _ptr(km), _ptr(out), N, S, num_heads, hd, float(hd) ** -0.5,
-                                         _stream()), 'clv_attn_probs_mean')
+    check(fn(_ptr(qkv), _ptr(km), _ptr(out), N, S, num_heads, hd, float(hd) ** -0.5, _stream()), name)
     return out
 
 

@@ -701,6 +701,31 @@ int clv_qa_choice_assemble_bwd(const void* dfeat, void* dvisual, void* dtext, in
  * softmax(q_h k_h^T * scale + kmask).  S <= 4096, hd <= 128 and even. */
 int clv_attn_probs_mean(const void* qkv, const float* kmask, float* out, int32_t N, int32_t S, int32_t nH, int32_t hd,
                         float scale, void* stream);
+/* The fp32-storage forms of the entries above, for parity mode (CLOVER_PARITY: fp32 storage and fp32 arithmetic, as
+ * clv_attn_f32_fwd / _bwd): the SAME kernel bodies instantiated with float activations, so the same arithmetic, the same
+ * dropout mask of (seed, row, column), the same limits (clv_qa_head_supported; S <= 4096, hd <= 128 and even) and return
+ * codes as their 16-bit counterparts, argument for argument.
+ *   clv_qa_head_f32_fwd / _bwd (qa_head.py:8-85): x and dx_full are fp32 rows of width D; the input gradient is stored
+ *     unrounded at rows[i].
+ *   clv_qa_choice_assemble_f32 / _f32_bwd (multimodal_transformer_finetune.py:87-123, :90-95 the expand over the
+ *     candidates): 16-byte copies of 4 floats, so D % 4 == 0; dvisual = the fp32 sum over the C candidates, stored as it
+ *     is (no rounding at all).
+ *   clv_attn_probs_mean_f32 (multimodal_transformer_finetune.py:157-193, :189 the head mean): qkv fp32 [N][S][3 nH hd]. */
+int clv_qa_head_f32_fwd(const float* x, const int32_t* rows, const float* w1, const float* b1, const float* gamma,
+                        const float* beta, const float* w2, const float* b2, const uint64_t* seed, float drop_p,
+                        float eps, float* z, float* g, float* mean, float* rstd, float* logits, int32_t M, int32_t D,
+                        int32_t H, int32_t K, void* stream);
+int clv_qa_head_f32_bwd(const float* x, const int32_t* rows, const float* w1, const float* gamma, const float* beta,
+                        const float* w2, const float* z, const float* g, const float* mean, const float* rstd,
+                        const float* dl, const float* s1, const float* s2, const uint64_t* seed, float drop_p, float* dy,
+                        float* dz, float* dx_full, float* dw1, float* db1, float* dgamma, float* dbeta, float* dw2,
+                        float* db2, int32_t M, int32_t D, int32_t H, int32_t K, void* stream);
+int clv_qa_choice_assemble_f32(const float* visual, const float* text, float* feat, int32_t B, int32_t C, int32_t n_vis,
+                               int32_t L, int32_t D, void* stream);
+int clv_qa_choice_assemble_f32_bwd(const float* dfeat, float* dvisual, float* dtext, int32_t B, int32_t C, int32_t n_vis,
+                                   int32_t L, int32_t D, void* stream);
+int clv_attn_probs_mean_f32(const float* qkv, const float* kmask, float* out, int32_t N, int32_t S, int32_t nH,
+                            int32_t hd, float scale, void* stream);
 
 /* Text -> video retrieval ranks without the score matrix (the metric of mmaction/core/evaluation/accuracy.py:430-462 with
  * normalize_fn of mmaction/utils/numpy_norm.py:5-8).  query fp32 [Nq][D] (row stride ldq), gallery fp32 [Ng][D] (ldg): rows
