@@ -391,7 +391,7 @@ class CloverEngine:
             tables.append(ops.sumsq_range_table(ranges, seg.flat_g.device))
         self._norm_state = ops.FusedNormState()
         for sk, _, _, _ in fresh.values():
-            sk._clv_ssq = (self.sumsq, slots, self._norm_state)
+            sk._clv_ssq = ops.NormSlots(self.sumsq, slots, self._norm_state)
         self._norm_tables = tables
 
     # ------------------------------------------------------------------ gradient clearing

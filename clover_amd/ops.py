@@ -56,6 +56,12 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _half_rows(t, cols):
+    """t as contiguous rows [-1, cols] of the 16-bit storage type (an upstream gradient on its way into a kernel)."""
+    t = t.reshape(-1, cols)
+    return _c(t if t.dtype == BF16 else t.to(BF16))
+
+
 ACTIVE_LOSS_SCALE = [1.0]    # the loss scale of the backward pass that is RUNNING (set by _ScaleGrad at its root, reset at its end)
 
 
@@ -243,6 +249,13 @@ class FusedNormState:
         self.dirty = False
 
 
+class NormSlots(NamedTuple):
+    """``_clv_ssq`` of a sink in fused-norm mode (engine._setup_fused_norm)."""
+    acc: Any                # the engine's sum-of-squares accumulator (an explicit pass over the sink adds to it)
+    slots: Any              # the CLV_SUMSQ_SLOTS partial sums the grouped / fold kernels add to
+    state: FusedNormState
+
+
 class FirstTouch:
     """State of an engine's first-touch gradient sinks (engine._setup_first_touch): ``on`` and the set of sinks already
     written since the engine last "cleared" the gradients.  The sink tensors (``param._clv_grad``) carry it as
@@ -272,6 +285,46 @@ def first_touch(dw_out):
     return True
 
 
+def _sinks(*params, pad=False):
+    """The gradient sinks of a GROUP of parameters whose gradients one backward produces together: a tuple aligned with
+    `params` (None where the parameter is None: an absent bias) when EVERY present one has a usable sink — the backward
+    then writes straight into them, calls _delivered() and returns None to autograd — else None: it allocates
+    temporaries and returns them.  All or nothing, so a group never splits between the two routes.
+
+    A sink is the engine's fp32 slab view ``param._clv_grad`` (pad=True: ``_clv_pad_grad``, the phantom-padded view the
+    MLM decoder's kernels write).  It is usable when it is fp32 and contiguous: the kernels write fp32 through the raw
+    pointer, so any other tensor was never a correct target, and the engine never produces one (engine._Segment).
+    What comes back is the ATTRIBUTE OBJECT, never a view of it: the first-touch state (``_clv_ft``, keyed on id() in
+    first_touch()) and the fused-norm slots (``_clv_ssq``) hang on that object, and a view carries neither.
+
+    Groups: (weight, bias) of a Linear — _LinearF32, _param_grads (_Linear, _MlpGelu, both _FusedMLP bodies), _MLMDecoder
+    (pad); (weight, bias, gamma, beta) of a LayerNorm-folded projection — _unfold_grads, _wgrad_folded; (gamma, beta) —
+    _LayerNorm, _MergeLayerNorm; (weight, bias, gamma, beta, mask_token) — _PatchEmbed.  One parameter at a time
+    (_sink): _Embedding, the table of _Attention, each of the six parameters of _QAHead."""
+    attr = '_clv_pad_grad' if pad else '_clv_grad'
+    out = []
+    for p in params:
+        sk = getattr(p, attr, None)
+        if p is not None and (sk is None or sk.dtype != torch.float32 or not sk.is_contiguous()):
+            return None
+        out.append(sk)
+    return tuple(out)
+
+
+def _sink(param):
+    """The usable sink of ONE parameter (see _sinks), or None."""
+    sks = _sinks(param)
+    return sks[0] if sks is not None else None
+
+
+def _delivered(*params):
+    """The gradients of `params` (None entries skipped) are complete in their sinks: the bucket countdown of the gradient
+    all-reduce (``_clv_ready``; a fused view's fans out to its members), once per parameter."""
+    for p in params:
+        if p is not None:
+            p._clv_ready()
+
+
 def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
     """dW fp32 [N,K] and db fp32 [N] of y = x W^T + b for bf16 dy2 [M,N], x2 [M,K].
     With dw_out / db_out (fp32, e.g. views of the engine's flat gradient slab) the result is
@@ -288,7 +341,7 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
     if ssq is not None and not first:
         # a SECOND gradient for a sink whose sum of squares rode on its first one (a caller running two backward passes
         # between optimizer steps): the fused sums no longer describe the slab — the engine recomputes the whole norm
-        ssq[2].dirty = True
+        ssq.state.dirty = True
         ssq = None
     if xstats is not None and not _wgrad_custom(M, N, K):
         x2 = ((x2.float() - xstats[0][:, None]) * xstats[1][:, None]).to(BF16)
@@ -319,14 +372,14 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
             else:
                 check(L.clv_linear_wgrad(*args, 0, _stream()), 'clv_linear_wgrad')
                 if ssq is not None:
-                    sumsq_accumulate(dw, ssq[0])
+                    sumsq_accumulate(dw, ssq.acc)
         else:                                  # one event pair per device kernel
             kname = 'wgrad_kernel' if xstats else f"wgrad_dma2_kernel<{'true' if slices == 1 else 'false'}>"
             with _Timed(kname, 2 * M * N * K, M * (N + K) * 2):
                 check(L.clv_linear_wgrad(*args, 1, _stream()), 'clv_linear_wgrad')
             check(L.clv_linear_wgrad(*args, 2, _stream()), 'clv_linear_wgrad')
             if ssq is not None:
-                sumsq_accumulate(dw, ssq[0])
+                sumsq_accumulate(dw, ssq.acc)
         return (None, None) if sink else (dw, db)
     # library GEMM with fp32 output: accumulated in place into the gradient slab view (beta = 1) — no bf16 rounding
     # of dW and no separate fp32 add
@@ -344,7 +397,7 @@ def linear_wgrad(dy2, x2, want_bias, dw_out=None, db_out=None, xstats=None):
         else:
             torch.addmm(dw_out, dy2.t(), x2, out_dtype=torch.float32, out=dw_out)
         if ssq is not None:
-            sumsq_accumulate(dw_out.reshape(-1), ssq[0])
+            sumsq_accumulate(dw_out.reshape(-1), ssq.acc)
         return None, None
     return torch.mm(dy2.t(), x2, out_dtype=torch.float32), db
 
@@ -486,7 +539,7 @@ def flush_wgrads(pending):
         slots = None                                 # norm slots of the sinks whose sum of squares the kernels deliver
         for e, it in zip(arr, chunk):
             if it.flags & DELIVER_SUMSQ:
-                slots = it.dw._clv_ssq[1]
+                slots = it.dw._clv_ssq.slots
             if e.work_floats == 0:                   # few-row problem: accumulated in place, nothing to fold
                 e.dw, e.db = it.dw.data_ptr(), (it.db.data_ptr() if it.db is not None else None)
                 e.overwrite = it.flags & (STORE_DW | DELIVER_SUMSQ)
@@ -524,7 +577,7 @@ def flush_folds(pending):
             e.partial, e.dw, e.db = it.partial.data_ptr(), it.dw.data_ptr(), (it.db.data_ptr() if it.db is not None else None)
             e.nk, e.e2, e.splits, e.overwrite = it.N * it.K, it.N * it.K + it.N, it.splits, it.flags
             if it.flags & DELIVER_SUMSQ:             # the fold delivers this sink's sum of squares (fused gradient norm)
-                slots = it.dw._clv_ssq[1]
+                slots = it.dw._clv_ssq.slots
         check(_lib.lib().clv_wgrad_fold_batch_ss(arr, len(chunk), _ptr(slots), _stream()), 'clv_wgrad_fold_batch')
 
 
@@ -628,6 +681,15 @@ def gemm_nt_fp8(a, b, bias=None, epilogue=None, aq8=None):
     return (c, c2) if c2 is not None else c
 
 
+def _raw_bf16(p):
+    """The 16-bit copy of a parameter (None for None): the engine's shadow (kept fresh by the AdamW kernel) or a cast on
+    the spot."""
+    if p is None:
+        return None
+    pb = getattr(p, '_clv_shadow', None)
+    return pb if pb is not None else p.detach().to(BF16)
+
+
 def _wt(weight, wb):
     """bf16 W^T [K,N]: the engine's transposed shadow (refreshed once per step) or a transpose on the spot."""
     wt = getattr(weight, '_clv_shadow_t', None) if weight is not None else None
@@ -706,13 +768,13 @@ class _LinearF32(torch.autograd.Function):
             dx = torch.empty(M, K, device=dy2.device, dtype=torch.float32)
             _sgemm_strided(dy2, (N, 1), w, (1, K), None, dx, M, K, N, False)          # dx[m][k] = sum_n dy[m][n] W[n][k]
             dx = dx.view(ctx.xshape)
-        wsink = getattr(weight, '_clv_grad', None)
-        bsink = getattr(bias, '_clv_grad', None) if bias is not None else None
-        sink = wsink is not None and wsink.dtype == torch.float32 and (bias is None or bsink is not None)
-        dw = wsink if sink else torch.empty(N, K, device=dy2.device, dtype=torch.float32)
-        db = None
-        if bias is not None:
-            db = bsink if sink else torch.empty(N, device=dy2.device, dtype=torch.float32)
+        sinks = _sinks(weight, bias)
+        sink = sinks is not None
+        if sink:
+            dw, db = sinks
+        else:
+            dw = torch.empty(N, K, device=dy2.device, dtype=torch.float32)
+            db = torch.empty(N, device=dy2.device, dtype=torch.float32) if bias is not None else None
         if bias is not None and M <= 96:
             # dW[n][k] (+)= sum_m dy[m][n] x[m][k] and db[n] (+)= sum_m dy[m][n] in ONE launch (the row sums of the A operand)
             check(_lib.lib().clv_sgemm_strided_rowsum(_ptr(dy2), _ptr(x2), _ptr(dw), _ptr(db), N, K, M, 1, N, 1, K,
@@ -723,26 +785,13 @@ class _LinearF32(torch.autograd.Function):
                 ones = _ones_f32(M, dy2.device)
                 _sgemm_strided(dy2, (1, N), ones, (0, 1), None, db.view(N, 1), N, 1, M, sink)   # db[n] (+)= sum_m dy[m][n]
         if sink:
-            weight._clv_ready()
-            if bias is not None:
-                bias._clv_ready()
+            _delivered(weight, bias)
             return dx, None, None
         return dx, dw.to(weight.dtype), (db.to(bias.dtype) if db is not None else None)
 
 
 def linear_f32(x, weight, bias=None):
     return _LinearF32.apply(x, weight, bias)
-
-
-def _sink_or_return(param, grad):
-    """Accumulate `grad` into an engine-managed parameter's flat-slab view (returns None), or hand it
-    back to autograd."""
-    sink = getattr(param, '_clv_grad', None)
-    if sink is not None:
-        sink.add_(grad.view_as(sink))
-        param._clv_ready()
-        return None
-    return grad.to(param.dtype)
 
 
 class _Linear(torch.autograd.Function):
@@ -759,14 +808,7 @@ class _Linear(torch.autograd.Function):
     def forward(ctx, x, weight, bias, xq=None):
         _need_gpu(x, weight)
         xb = x if x.dtype == BF16 else x.to(BF16)
-        wb = getattr(weight, '_clv_shadow', None)
-        if wb is None:
-            wb = weight.to(BF16)
-        bb = None
-        if bias is not None:
-            bb = getattr(bias, '_clv_shadow', None)
-            if bb is None:
-                bb = bias.to(BF16)
+        wb = _raw_bf16(weight)
         N, K = wb.shape
         x2 = xb.reshape(-1, K)
         if _rowgemm_fwd_ok(xb, N, K):
@@ -779,10 +821,8 @@ class _Linear(torch.autograd.Function):
                         epilogue=GEMM_EPI_BIAS if bias is not None else GEMM_EPI_NONE).view(xb.shape[:-1] + (N,))
         else:
             _library_gemm('linear', (x2.shape[0], N, K))
-            y = torch.nn.functional.linear(xb, wb, bb)
+            y = torch.nn.functional.linear(xb, wb, _raw_bf16(bias))
         ctx.save_for_backward(xb, wb)
-        ctx.has_bias = bias is not None
-        ctx.wdtype = weight.dtype
         ctx.wref, ctx.bref = weight, bias
         return y
 
@@ -790,34 +830,16 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, dy):
         xb, wb = ctx.saved_tensors
         N, K = wb.shape
-        dy2 = dy.reshape(-1, N)
-        if dy2.dtype != BF16:
-            dy2 = dy2.to(BF16)
-        dy2 = _c(dy2)
+        dy2 = _half_rows(dy, N)
         x2 = _c(xb.reshape(-1, K))
         dx = linear_dgrad(dy2, wb, ctx.wref).view(xb.shape) if ctx.needs_input_grad[0] else None
         dw, db = (None, None)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            wsink = getattr(ctx.wref, '_clv_grad', None)
-            bsink = getattr(ctx.bref, '_clv_grad', None) if ctx.has_bias else None
-            if wsink is not None and (bsink is not None or not ctx.has_bias):
-                linear_wgrad(dy2, x2, ctx.has_bias, wsink, bsink)
-                ctx.wref._clv_ready()
-                if ctx.has_bias:
-                    ctx.bref._clv_ready()
-            else:
-                dw, db = linear_wgrad(dy2, x2, ctx.has_bias)
-                dw = dw.to(ctx.wdtype)
-                db = db.to(ctx.wdtype) if db is not None else None
+        if ctx.needs_input_grad[1] or (ctx.bref is not None and ctx.needs_input_grad[2]):
+            dw, db = _param_grads(dy2, x2, ctx.wref, ctx.bref)
         return dx, dw, db, None
 
 
 _NOAFFINE_CONST = {}
-
-
-def _raw_bf16(w):
-    wb = getattr(w, '_clv_shadow', None)
-    return wb if wb is not None else w.detach().to(BF16)
 
 
 def _ln_bwd_noaffine(dxhat, x, mean, rstd, dsum, gamma=None, xscale=None, rows_per_sample=1):
@@ -837,11 +859,7 @@ def _ln_bwd_noaffine(dxhat, x, mean, rstd, dsum, gamma=None, xscale=None, rows_p
     if gamma is not None:
         ones = _c(gamma.detach().float())
     dx = torch.empty_like(x)
-    ds2 = None
-    if dsum is not None:
-        ds2 = _c(dsum).view(rows, C_)
-        if ds2.dtype != BF16:
-            ds2 = ds2.to(BF16)
+    ds2 = _half_rows(dsum, C_) if dsum is not None else None
     # xscale: x is the saved SUM t = xscale * a + r (x_is_sum); dx then receives d t times the factor (the gradient of a)
     # and dres d t itself (the gradient of r) — both from the one kernel
     dres = torch.empty_like(x) if xscale is not None else None
@@ -870,10 +888,8 @@ def _unfold_grads(dwf, dbf, weight, bias, gamma, beta):
     """Backward of fold_layernorm: (d wf, d bf) -> gradients of (weight, bias, gamma, beta), accumulated straight into
     the engine's slab views when all four are engine-managed (returns Nones), else returned."""
     N, K = weight.shape
-    ps = (weight, bias, gamma, beta)
-    sinks = [getattr(q, '_clv_grad', None) if q is not None else None for q in ps]
-    use_sink = all(sk is not None and sk.dtype == torch.float32 for sk, q in zip(sinks, ps) if q is not None)
-    if use_sink:
+    sinks = _sinks(weight, bias, gamma, beta)
+    if sinks is not None:
         dw, db, dg, dbt = sinks
     else:
         dw = torch.zeros(N, K, device=dwf.device, dtype=torch.float32)
@@ -883,10 +899,8 @@ def _unfold_grads(dwf, dbf, weight, bias, gamma, beta):
     check(_lib.lib().clv_ln_fold_bwd(_ptr(dwf), _ptr(dbf), _ptr(_c(weight.detach().float())),
                                      _ptr(_c(gamma.detach().float())), _ptr(_c(beta.detach().float())), _ptr(dw), _ptr(db),
                                      _ptr(dg), _ptr(dbt), N, K, _stream()), 'clv_ln_fold_bwd')
-    if use_sink:
-        for q in ps:
-            if q is not None:
-                q._clv_ready()
+    if sinks is not None:
+        _delivered(weight, bias, gamma, beta)
         return None, None, None, None
     return (dw.to(weight.dtype), db.to(bias.dtype) if bias is not None else None, dg.to(gamma.dtype),
             dbt.to(beta.dtype))
@@ -896,10 +910,8 @@ def _wgrad_folded(dy2, xhat, xs, mean, rstd, weight, bias, gamma, beta):
     """Weight gradient of a LayerNorm-folded projection and its un-fold into (d weight, d bias, d gamma, d beta).  Inside
     defer_folds() with engine-managed parameters both are deferred: the GEMM joins the grouped launch (into a zeroed
     temporary), the un-fold kernel runs after the folds."""
-    ps = (weight, bias, gamma, beta)
     if (SEGMENT is not None and SEGMENT.wgrads is not None and xhat is not None
-            and all(getattr(q, '_clv_grad', None) is not None and q._clv_grad.dtype == torch.float32
-                    for q in ps if q is not None)):
+            and _sinks(weight, bias, gamma, beta) is not None):
         (M, N), K = dy2.shape, xhat.shape[1]
         if _wgrad_custom(M, N, K):
             in_place = bool(_lib.lib().clv_linear_wgrad_in_place(M, N, K))
@@ -943,9 +955,7 @@ class _FusedLNLinear(torch.autograd.Function):
     def backward(ctx, dy, ds):
         xs, mean, rstd, wt, xhat = ctx.saved_tensors
         N, K = wt.shape
-        dy2 = _c(dy.reshape(-1, N))
-        if dy2.dtype != BF16:
-            dy2 = dy2.to(BF16)
+        dy2 = _half_rows(dy, N)
         weight, bias, gamma, beta = ctx.prefs
         # through the raw weight (the engine keeps its transpose fresh); the norm's gamma is applied by the LN backward
         dxhat = linear_dgrad(dy2, _raw_bf16(weight), weight)
@@ -1031,9 +1041,7 @@ class _FusedMLP(torch.autograd.Function):
         xsc = _c(x_scale.detach().float()) if x_scale is not None else None
         rps = a2.shape[0] // a.shape[0]
         ctx.xsc, ctx.rps = xsc, rps
-        w2b = getattr(w2, '_clv_shadow', None)
-        if w2b is None:
-            w2b = w2.to(BF16)
+        w2b = _raw_bf16(w2)
         ctx.has_res = r is not None
         ctx.shape = a.shape
         ctx.w2ref, ctx.b2ref = w2, b2
@@ -1049,17 +1057,12 @@ class _FusedMLP(torch.autograd.Function):
         o1 = rowgemm(a2, wt1, bf1, res=r2, standardise=True, epilogue=1, eps=eps, want_xhat=any(ctx.needs_input_grad),
                      xscale=xsc, rows_per_sample=rps)
         xs = o1['sum'] if r is not None else a2
-        b2b = None
-        if b2 is not None:
-            b2b = getattr(b2, '_clv_shadow', None)
-            if b2b is None:
-                b2b = b2.to(BF16)
         if own_gemm_ok(o1['y'], w2b.shape[0], w2b.shape[1]):     # fc2 of the stage-0 block (200 704 x 96 x 384)
             out = gemm_nt(o1['y'], w2b, b2.detach() if b2 is not None else None,
                           epilogue=GEMM_EPI_BIAS if b2 is not None else GEMM_EPI_NONE)
         else:
             _library_gemm('fused_mlp fc2', (o1['y'].shape[0], w2b.shape[0], w2b.shape[1]))
-            out = torch.nn.functional.linear(o1['y'], w2b, b2b)
+            out = torch.nn.functional.linear(o1['y'], w2b, _raw_bf16(b2))
         ctx.save_for_backward(xs, o1['mean'], o1['rstd'], wt1, o1['pre'], o1['y'], w2b, o1['xhat'])
         return out.view(a.shape), (o1['sum'].view(a.shape) if r is not None else None)
 
@@ -1069,9 +1072,7 @@ class _FusedMLP(torch.autograd.Function):
             return _FusedMLP._backward_one_kernel(ctx, dout, ds)
         xs, mean, rstd, wt1, pre, act, w2b, xhat = ctx.saved_tensors
         C_, Hd = w2b.shape                              # fc2: [C, 4C]
-        do2 = _c(dout.reshape(-1, C_))
-        if do2.dtype != BF16:
-            do2 = do2.to(BF16)
+        do2 = _half_rows(dout, C_)
         # d pre = (d out . W2) * gelu'(pre)
         if rowgemm_supported(Hd, C_) and C_ <= 288:
             dpre = rowgemm(do2, _wt(ctx.w2ref, w2b), None, epilogue=2, pre_in=pre)['y']
@@ -1080,20 +1081,7 @@ class _FusedMLP(torch.autograd.Function):
             dact = torch.mm(do2, w2b)
             dpre = torch.empty_like(dact)
             check(_lib.lib().clv_gelu_bwd(_ptr(dact), _ptr(pre), _ptr(dpre), dact.numel(), 0, _stream()), 'clv_gelu_bwd')
-        # fc2 parameter gradients
-        w2, b2 = ctx.w2ref, ctx.b2ref
-        wsink = getattr(w2, '_clv_grad', None)
-        bsink = getattr(b2, '_clv_grad', None) if b2 is not None else None
-        dw2 = db2 = None
-        if wsink is not None and (bsink is not None or b2 is None):
-            linear_wgrad(do2, act, b2 is not None, wsink, bsink)
-            w2._clv_ready()
-            if b2 is not None:
-                b2._clv_ready()
-        else:
-            dw2, db2 = linear_wgrad(do2, act, b2 is not None)
-            dw2 = dw2.to(w2.dtype)
-            db2 = db2.to(b2.dtype) if db2 is not None else None
+        dw2, db2 = _param_grads(do2, act, ctx.w2ref, ctx.b2ref)
         # fc1 + LayerNorm
         w1, b1, gamma, beta = ctx.prefs
         dxhat = linear_dgrad(dpre, _raw_bf16(w1), w1)
@@ -1113,14 +1101,8 @@ class _FusedMLP(torch.autograd.Function):
         for the (grouped, deferred) weight-gradient launches."""
         xs, mean, rstd, wt1, bf1, w2b = ctx.saved_tensors
         C_, Hd = w2b.shape
-        do2 = _c(dout.reshape(-1, C_))
-        if do2.dtype != BF16:
-            do2 = do2.to(BF16)
-        ds2 = None
-        if ds is not None:
-            ds2 = _c(ds).view(-1, C_)
-            if ds2.dtype != BF16:
-                ds2 = ds2.to(BF16)
+        do2 = _half_rows(dout, C_)
+        ds2 = _half_rows(ds, C_) if ds is not None else None
         w2, b2 = ctx.w2ref, ctx.b2ref
         o = mlp_fused_bwd(xs, mean, rstd, do2, ds2, wt1, bf1, _c(_wt(w2, w2b)), ctx.xsc, ctx.rps,
                           want_dres=ctx.xsc is not None and ctx.has_res)
@@ -1163,13 +1145,10 @@ def linear(x, weight, bias=None):
 
 def _param_grads(dy2, x2, weight, bias):
     """dW / db of one Linear into the engine's slab views (-> None, None) or returned to autograd."""
-    wsink = getattr(weight, '_clv_grad', None)
-    bsink = getattr(bias, '_clv_grad', None) if bias is not None else None
-    if wsink is not None and (bsink is not None or bias is None):
-        linear_wgrad(dy2, x2, bias is not None, wsink, bsink)
-        weight._clv_ready()
-        if bias is not None:
-            bias._clv_ready()
+    sinks = _sinks(weight, bias)
+    if sinks is not None:
+        linear_wgrad(dy2, x2, bias is not None, *sinks)
+        _delivered(weight, bias)
         return None, None
     dw, db = linear_wgrad(dy2, x2, bias is not None)
     return dw.to(weight.dtype), (db.to(bias.dtype) if db is not None else None)
@@ -1184,10 +1163,7 @@ class _MlpGelu(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, xq=None):
         K = x.shape[-1]
         x2 = x.reshape(-1, K)
-        w1b = getattr(w1, '_clv_shadow', None)
-        w1b = w1b if w1b is not None else w1.to(BF16)
-        w2b = getattr(w2, '_clv_shadow', None)
-        w2b = w2b if w2b is not None else w2.to(BF16)
+        w1b, w2b = _raw_bf16(w1), _raw_bf16(w2)
         # the second output is GELU'(pre) rather than pre when fc2's input gradient runs on clv_gemm_nt too: its
         # epilogue then is one multiply per element (no erf / exp in the backward)
         Hd, C_ = w1b.shape[0], w2b.shape[0]
@@ -1204,8 +1180,7 @@ class _MlpGelu(torch.autograd.Function):
                           epilogue=GEMM_EPI_BIAS if b2 is not None else GEMM_EPI_NONE)
         else:
             _library_gemm('mlp_gelu fc2', (act.shape[0], C_, Hd))
-            b2b = getattr(b2, '_clv_shadow', None) if b2 is not None else None
-            out = torch.nn.functional.linear(act, w2b, b2b if b2b is not None or b2 is None else b2.to(BF16))
+            out = torch.nn.functional.linear(act, w2b, _raw_bf16(b2))
         ctx.save_for_backward(x2, pre, act, w1b, w2b)
         ctx.refs = (w1, b1, w2, b2)
         ctx.xshape = x.shape
@@ -1215,9 +1190,7 @@ class _MlpGelu(torch.autograd.Function):
     def backward(ctx, dout):
         x2, pre, act, w1b, w2b = ctx.saved_tensors
         w1, b1, w2, b2 = ctx.refs
-        do2 = _c(dout.reshape(-1, w2b.shape[0]))
-        if do2.dtype != BF16:
-            do2 = do2.to(BF16)
+        do2 = _half_rows(dout, w2b.shape[0])
         if ctx.dgelu_saved:                                  # pre holds GELU'(pre)
             dpre = gemm_nt(do2, _wt(w2, w2b), aux=pre, epilogue=GEMM_EPI_MUL)
         else:
@@ -1449,11 +1422,10 @@ class _LayerNorm(torch.autograd.Function):
         dx = torch.empty_like(x2)
         xform = xs is not None or ctx.drop_p > 0
         dres = torch.empty_like(x2) if (xform and ctx.has_res) else None
-        gsink = getattr(ctx.gref, '_clv_grad', None)
-        bsink = getattr(ctx.bref, '_clv_grad', None)
-        sink = gsink is not None and bsink is not None and gsink.dtype == torch.float32
+        sinks = _sinks(ctx.gref, ctx.bref)
+        sink = sinks is not None
         if sink:
-            dg, db = gsink, bsink
+            dg, db = sinks
         else:
             dg = torch.zeros(C_, device=x2.device, dtype=torch.float32)
             db = torch.zeros_like(dg)
@@ -1473,8 +1445,7 @@ class _LayerNorm(torch.autograd.Function):
         if ctx.has_res:
             drv = dres.view(ctx.xshape) if dres is not None else dxv
         if sink:
-            ctx.gref._clv_ready()
-            ctx.bref._clv_ready()
+            _delivered(ctx.gref, ctx.bref)
             return dxv, drv, None, None, None, None, None, None, None
         return dxv, drv, dg.to(ctx.gdtype), db.to(ctx.gdtype), None, None, None, None, None
 
@@ -1542,17 +1513,16 @@ class _MergeLayerNorm(torch.autograd.Function):
         x2, r2, g, mean, rstd, xs = ctx.saved_tensors
         B, D, H2, W2, Cs = ctx.geom
         rows, C_ = B * D * H2 * W2, 4 * Cs
-        dy2 = _c(dy if dy.dtype == BF16 else dy.to(BF16))
+        dy2 = _half_rows(dy, C_)
         L = _lib.lib()
         nblk = L.clv_layernorm_bwd_blocks(rows, C_)
         partial = torch.empty(2 * nblk * C_, device=x2.device, dtype=torch.float32)
         dx = torch.empty_like(x2)
         dres = torch.empty_like(x2) if (xs is not None and r2 is not None) else None
-        gsink = getattr(ctx.gref, '_clv_grad', None)
-        bsink = getattr(ctx.bref, '_clv_grad', None)
-        sink = gsink is not None and bsink is not None and gsink.dtype == torch.float32
+        sinks = _sinks(ctx.gref, ctx.bref)
+        sink = sinks is not None
         if sink:
-            dg, db = gsink, bsink
+            dg, db = sinks
         else:
             dg = torch.zeros(C_, device=x2.device, dtype=torch.float32)
             db = torch.zeros_like(dg)
@@ -1562,8 +1532,7 @@ class _MergeLayerNorm(torch.autograd.Function):
               'clv_layernorm_bwd')
         drv = None if r2 is None else (dres if dres is not None else dx)
         if sink:
-            ctx.gref._clv_ready()
-            ctx.bref._clv_ready()
+            _delivered(ctx.gref, ctx.bref)
             return dx, drv, None, None, None, None
         return dx, drv, dg.to(ctx.gdtype), db.to(ctx.gdtype), None, None
 
@@ -1694,14 +1663,14 @@ class _Embedding(torch.autograd.Function):
     def backward(ctx, dy):
         (ids,) = ctx.saved_tensors
         w = ctx.wref
-        sink = getattr(w, '_clv_grad', None)
+        sink = _sink(w)
         flat = ids.reshape(-1)
         d = dy.reshape(-1, dy.shape[-1])
         if ctx.pad is not None:
             d = d.masked_fill((flat == ctx.pad)[:, None], 0)
         if sink is not None:
-            sink.index_add_(0, flat, d.to(sink.dtype))
-            w._clv_ready()
+            sink.index_add_(0, flat, d.float())
+            _delivered(w)
             return None, None, None
         return None, torch.zeros_like(w).index_add_(0, flat, d.to(w.dtype)), None
 
@@ -1762,9 +1731,7 @@ class _Attention(torch.autograd.Function):
         g.work = seq_work.data_ptr() if seq_work is not None else None
         dtab = work = sink = None
         if tab is not None:
-            sink = getattr(ctx.tref, '_clv_grad', None)
-            if sink is not None and (sink.dtype != torch.float32 or not sink.is_contiguous()):
-                sink = None
+            sink = _sink(ctx.tref)
             dtab = sink if sink is not None else torch.zeros_like(tab)
             work = torch.empty(L.clv_attn_bwd_work_bytes(C.byref(g)), device=qkv.device, dtype=torch.uint8)
             g.dbias_index = _dbias_index(g, qkv.device)
@@ -1799,7 +1766,7 @@ class _Attention(torch.autograd.Function):
             with _Timed(_kname('attn_bwd_dkv_kernel', g), fl * 0.6, by * 0.5):
                 check(L.clv_attn_bwd(*args, 4, C.byref(g), _stream()), 'clv_attn_bwd')
         if sink is not None:
-            ctx.tref._clv_ready()
+            _delivered(ctx.tref)
             dtab = None
         elif dtab is not None:
             dtab = dtab.to(ctx.tref.dtype)
@@ -2020,10 +1987,7 @@ class _PatchEmbed(torch.autograd.Function):
         L = _lib.lib()
 
         def bf(t):
-            if t is None:
-                return None
-            t = _c(t.reshape(M, Cout))
-            return t if t.dtype == BF16 else t.to(BF16)
+            return _half_rows(t, Cout) if t is not None else None
         if ctx.stacked:                  # dclean holds the gradient of the stacked [2B, ...] output
             dclean, dmasked = (dclean[:B], dclean[B:]) if dclean is not None else (None, None)
         dc = bf(dclean) if want_clean else None
@@ -2033,16 +1997,17 @@ class _PatchEmbed(torch.autograd.Function):
         # deferred grouped launch) — this backward closes the video encoder's chain, and a dozen zero-fill / add kernels of
         # autograd's AccumulateGrad sat on the critical path here
         weight, bias, gamma, beta, mask_token = ctx.prefs
-        ps = [q for q in (weight, bias, gamma, beta, mask_token if dm is not None else None) if q is not None]
-        sink = all(getattr(q, '_clv_grad', None) is not None and q._clv_grad.dtype == torch.float32
-                   and q._clv_grad.is_contiguous() for q in ps) and (gf is None) == (gamma is None)
+        ps = (weight, bias, gamma, beta, mask_token if dm is not None else None)
+        sinks = _sinks(*ps)
+        sink = sinks is not None
+        if sink:
+            wsink, bsink, gsink, besink, msink = sinks
         if dm is None:
             dyb = dc
         else:
             # dy = d_clean + d_masked (1 - w), d mask_token = sum d_masked w — one kernel (clv_patch_embed_blend_bwd)
             dyb = torch.empty(M, Cout, device=xc.device, dtype=BF16)
-            dmt = (mask_token._clv_grad.view(-1) if sink
-                   else torch.zeros(Cout, device=xc.device, dtype=torch.float32))
+            dmt = msink.view(-1) if sink else torch.zeros(Cout, device=xc.device, dtype=torch.float32)
             check(L.clv_patch_embed_blend_bwd(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, T, H, W, Cout,
                                               vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd')
             dmt = None if sink else dmt.reshape(mtshape)
@@ -2051,7 +2016,7 @@ class _PatchEmbed(torch.autograd.Function):
             partial = torch.empty(2 * nblk * Cout, device=xc.device, dtype=torch.float32)
             dz = torch.empty_like(z)
             if sink:
-                dg, db = gamma._clv_grad.view(-1), beta._clv_grad.view(-1)
+                dg, db = gsink.view(-1), besink.view(-1)
             else:
                 dg = torch.zeros(Cout, device=xc.device, dtype=torch.float32)
                 db = torch.zeros_like(dg)
@@ -2065,9 +2030,12 @@ class _PatchEmbed(torch.autograd.Function):
         patches = torch.empty(M, 96, device=xc.device, dtype=BF16)
         check(L.clv_im2col_patches(_ptr(xc), _ptr(patches), B, T, H, W, _stream()), 'clv_im2col_patches')
         if sink:
-            linear_wgrad(dz, patches, True, weight._clv_grad.view(Cout, 96), bias._clv_grad.view(-1))
-            for q in ps:
-                q._clv_ready()
+            # the conv weight's sink goes in as its [Cout, 96] VIEW, not as the attribute object: a view carries neither
+            # first-touch state nor norm slots (_sinks), so this gradient always accumulates into a cleared slot and the
+            # norm pass reads it.  Kept as it was: engine._setup_first_touch finds the slot non-finite in its poisoned
+            # pass and goes on clearing it
+            linear_wgrad(dz, patches, True, wsink.view(Cout, 96), bsink.view(-1))
+            _delivered(*ps)
             return None, None, None, None, None, None, None, None, None, None
         dw, dbias = linear_wgrad(dz, patches, True)
         dw = dw.reshape(wshape)
@@ -2112,7 +2080,7 @@ class _MLMDecoder(torch.autograd.Function):
     def forward(ctx, x2, weight, bias):
         _need_gpu(x2, weight)
         V = weight.shape[0]
-        ctx.engine = hasattr(weight, '_clv_pad_shadow')
+        ctx.engine = _pad_managed(weight, bias)
         if ctx.engine:
             Wp, bp = weight._clv_pad_shadow, bias._clv_pad_weight
         else:
@@ -2153,9 +2121,8 @@ class _MLMDecoder(torch.autograd.Function):
             dyp[:, :V].copy_(dy)
         if ctx.engine:
             dx = gemm_nt(dyp, weight._clv_pad_shadow_t) if ctx.needs_input_grad[0] else None
-            linear_wgrad(dyp, xb, True, weight._clv_pad_grad, bias._clv_pad_grad)
-            weight._clv_ready()
-            bias._clv_ready()
+            linear_wgrad(dyp, xb, True, *_sinks(weight, bias, pad=True))
+            _delivered(weight, bias)
             return dx, None, None
         Wp = rest[0]
         dx = gemm_nt(dyp, Wp.t().contiguous()) if ctx.needs_input_grad[0] else None
@@ -2163,13 +2130,20 @@ class _MLMDecoder(torch.autograd.Function):
         return dx, dwp[:V].to(weight.dtype), dbp[:V].to(bias.dtype)
 
 
+def _pad_managed(weight, bias):
+    """Do both parameters carry the engine's phantom-padded views — the 16-bit weight and its transpose, the fp32 bias,
+    and a usable padded gradient sink each (_sinks)?"""
+    return (all(hasattr(weight, a) for a in ('_clv_pad_shadow', '_clv_pad_shadow_t')) and hasattr(bias, '_clv_pad_weight')
+            and _sinks(weight, bias, pad=True) is not None)
+
+
 def mlm_decoder_ok(x, weight, bias):
     """The own-kernel decoder: engine-managed parameters bring their phantom-padded views; without an engine the padded
     operands are built per call (hidden width a multiple of 64: whole GEMM stages).  Not the parity path."""
     if parity.enabled() or not x.is_cuda or bias is None:
         return False
-    if all(hasattr(weight, a) for a in ('_clv_pad_shadow', '_clv_pad_shadow_t', '_clv_pad_grad')):
-        return hasattr(bias, '_clv_pad_weight') and hasattr(bias, '_clv_pad_grad')
+    if _pad_managed(weight, bias):
+        return True
     return (not hasattr(weight, '_clv_pad_shadow') and weight.shape[1] % 64 == 0 and weight.shape[1] >= 64
             and x.shape[-1] == weight.shape[1])
 
@@ -2653,7 +2627,7 @@ def _qa_entry(name, t, what):
 
 def _qa_grad_out(p):
     """(fp32 buffer the head's backward ADDS the gradient of p into, whether it is the engine's slab sink)."""
-    sink = getattr(p, '_clv_grad', None)
+    sink = _sink(p)
     if sink is not None:
         return sink, True
     return torch.zeros(p.shape, device=p.device, dtype=torch.float32), False
@@ -2719,13 +2693,8 @@ class _QAHead(torch.autograd.Function):
         check(bwd(_ptr(h), _ptr(rows), _ptr(w1), _ptr(gamma), _ptr(beta), _ptr(w2), _ptr(zg[0]), _ptr(zg[1]),
                   _ptr(stats[0]), _ptr(stats[1]), _ptr(dl), _ptr(s1), _ptr(s2), _ptr(seed), drop_p, _ptr(scratch[0]),
                   _ptr(scratch[1]), _ptr(dh), *[_ptr(t) for t, _ in outs], M, D, H, K, _stream()), bwd_name)
-        grads = []
-        for p, (t, is_sink) in zip(ctx.params, outs):
-            if is_sink:
-                p._clv_ready()
-                grads.append(None)
-            else:
-                grads.append(t.to(p.dtype))
+        _delivered(*[p for p, (_, is_sink) in zip(ctx.params, outs) if is_sink])
+        grads = [None if is_sink else t.to(p.dtype) for p, (t, is_sink) in zip(ctx.params, outs)]
         return (dh, None, *grads, None, None, None, None, None)
 
 

@@ -595,6 +595,102 @@ def test_segment_lifecycle(monkeypatch):
     assert [k for k, _ in log] == ['wgrads', 'folds', 'ln_reduces', 'dbias_gathers'] and all(p == [] for _, p in log)
 
 
+def _sink_param(shape=(4, 8), sink_dtype=torch.float32):
+    """A CPU parameter carrying the engine's attributes by hand: a zeroed sink and a counting ``_clv_ready``."""
+    p = torch.nn.Parameter(torch.zeros(shape))
+    p._clv_grad = torch.zeros(shape, dtype=sink_dtype)
+    p.calls = []
+    p._clv_ready = lambda: p.calls.append(1)
+    return p
+
+
+def test_gradient_sink_group_decision():
+    """ops._sinks: all or nothing over a group — the ATTRIBUTE OBJECTS (aligned with the parameters, None for an absent
+    one) when every present parameter has an fp32, contiguous sink, else None; the pad variant reads ``_clv_pad_grad``;
+    ops._sink is the one-parameter form; a sink comes back still carrying its first-touch state."""
+    from clover_amd import ops
+    w, b, g = _sink_param(), _sink_param((4,)), _sink_param((8,))
+    got = ops._sinks(w, None, b, g)
+    assert isinstance(got, tuple) and len(got) == 4
+    assert got[0] is w._clv_grad and got[1] is None and got[2] is b._clv_grad and got[3] is g._clv_grad
+    assert ops._sinks(w) == (w._clv_grad,) and ops._sinks(w)[0] is w._clv_grad and ops._sinks() == () and ops._sinks(None) == (None,)
+    assert ops._sink(w) is w._clv_grad and ops._sink(None) is None
+    plain = torch.nn.Parameter(torch.zeros(4))
+    assert ops._sinks(w, plain) is None and ops._sinks(plain, w) is None and ops._sink(plain) is None
+    unset = _sink_param((4,))
+    unset._clv_grad = None
+    assert ops._sinks(w, unset) is None
+    for dt in (torch.float16, torch.bfloat16):
+        half = _sink_param((4,), dt)
+        assert ops._sinks(w, half, g) is None and ops._sink(half) is None
+    strided = _sink_param()
+    strided._clv_grad = torch.zeros(8, 4).t()
+    assert strided._clv_grad.shape == (4, 8) and not strided._clv_grad.is_contiguous()
+    assert ops._sinks(w, b, strided) is None and ops._sink(strided) is None
+    # identity: what hangs on the sink object is still there on what the helper hands out
+    st = ops.FirstTouch()
+    st.on = True
+    w._clv_grad._clv_ft = st
+    w._clv_grad._clv_ssq = ops.NormSlots(torch.zeros(1), torch.zeros(1), ops.FusedNormState())
+    sk = ops._sinks(w, b)[0]
+    assert sk._clv_ft is st and sk._clv_ssq.state.dirty is False and ops._sink(w)._clv_ft is st
+    assert ops.first_touch(sk) and not ops.first_touch(ops._sink(w))          # one state: the second touch accumulates
+    assert not ops.first_touch(w._clv_grad.view(8, 4))                           # (a view opts out: it carries no state)
+    # the phantom-padded variant reads the padded view and nothing else
+    assert ops._sinks(w, b, pad=True) is None
+    w._clv_pad_grad, b._clv_pad_grad = torch.zeros(6, 8), torch.zeros(6)
+    got = ops._sinks(w, b, pad=True)
+    assert got[0] is w._clv_pad_grad and got[1] is b._clv_pad_grad and ops._sinks(w, b)[0] is w._clv_grad
+    b._clv_pad_grad = torch.zeros(6, dtype=torch.bfloat16)
+    assert ops._sinks(w, b, pad=True) is None
+
+
+def test_gradient_sinks_delivered_once_each():
+    """ops._delivered: ``_clv_ready`` of every present parameter exactly once, None skipped; a fused view's (as
+    engine._Segment.fused_view builds it) reaches each member once."""
+    from clover_amd import ops
+    w, b, g = _sink_param(), _sink_param((4,)), _sink_param((8,))
+    ops._delivered(w, None, b)
+    assert (len(w.calls), len(b.calls), len(g.calls)) == (1, 1, 0)
+    ops._delivered()
+    ops._delivered(None, None)
+    assert (len(w.calls), len(b.calls), len(g.calls)) == (1, 1, 0)
+    q, k, v = _sink_param(), _sink_param(), _sink_param()
+    f = torch.nn.Parameter(torch.zeros(12, 8))
+    f._clv_grad = torch.zeros(12, 8)
+    f._clv_members = [q, k, v]
+    f._clv_ready = lambda ms=f._clv_members: [m._clv_ready() for m in ms] and None
+    assert ops._sinks(f, None) == (f._clv_grad, None)
+    ops._delivered(f, g)
+    assert [len(m.calls) for m in (q, k, v, g)] == [1, 1, 1, 1]
+
+
+def test_gradient_sink_census():
+    """Only the helpers read the sink attributes: in the code of clover_amd/ops.py — comments and docstrings aside —
+    ``_clv_grad`` appears in _sinks alone and ``_clv_ready`` in _delivered alone."""
+    import ast
+    import io
+    import tokenize
+    src = open(os.path.join(ROOT, 'clover_amd', 'ops.py')).read()
+    tree = ast.parse(src)
+    skip = set()                                # lines of docstrings
+    for node in ast.walk(tree):
+        if isinstance(node, (ast.Module, ast.ClassDef, ast.FunctionDef)) and ast.get_docstring(node, clean=False) is not None:
+            skip.update(range(node.body[0].lineno, node.body[0].end_lineno + 1))
+    owner = {}                                  # line -> name of the top-level function it lies in
+    for node in tree.body:
+        if isinstance(node, ast.FunctionDef):
+            owner.update((ln, node.name) for ln in range(node.lineno, node.end_lineno + 1))
+    found = {'_clv_grad': set(), '_clv_ready': set()}
+    for tok in tokenize.generate_tokens(io.StringIO(src).readline):
+        if tok.type == tokenize.COMMENT or tok.start[0] in skip:
+            continue
+        for name in found:
+            if re.search(r'(?<![A-Za-z0-9])%s(?![A-Za-z0-9_])' % name, tok.string):
+                found[name].add(owner.get(tok.start[0], '<module>:%d' % tok.start[0]))
+    assert found == {'_clv_grad': {'_sinks'}, '_clv_ready': {'_delivered'}}, found
+
+
 def test_segment_take_stream_wgrads(monkeypatch):
     """Segment.take_stream_wgrads (the by-stream split behind ops.flush_stream_wgrads): the items of one stream leave in
     their order, the others — those without a stream included — keep theirs; an absent stream takes nothing."""
