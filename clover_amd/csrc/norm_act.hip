@@ -1024,7 +1024,13 @@ __global__ void __launch_bounds__(128) ln_fold_fwd_kernel(const float* __restric
     float dot = 0.f;
     for (int k = threadIdx.x; k < K; k += 128) {
         const float v = w[(int64_t)n * K + k];
-        wf[(int64_t)n * K + k] = f2bf(v * gamma[k]);
+        // the fp32 product, THEN its rounding to 16 bits — what `(w * gamma).to(half)` gives anywhere else, and what the bf16
+        // build computes.  Left to the compiler, the f16 build turns product + conversion into one v_fma_mixlo_f16, which rounds
+        // the exact product once: one 16-bit ulp away wherever the fp32 rounding lands on a tie (2 of 27 648 elements at
+        // 288 x 96).  The empty asm keeps the product a value of its own.
+        float p = v * gamma[k];
+        asm volatile("" : "+v"(p));
+        wf[(int64_t)n * K + k] = f2bf(p);
         dot += v * beta[k];
     }
     dot = wave_sum(dot);
