@@ -3,6 +3,7 @@
 // Pure HBM streaming: 16 B per lane, grid-stride.
 #include "common.hpp"
 #include "../../include/clover_hip.h"
+#include "optim_state.hpp"
 
 namespace {
 
@@ -124,30 +125,7 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
     }
 }
 
-// Device-resident optimizer state (clv_optim_prep writes it, clv_adamw_step_dev reads it): the clip coefficient, Adam's
-// bias corrections and Adam's OWN step count t, which advances only on steps that are taken — the reference skips
-// optimizer.step() on a non-finite gradient (mmcv_Fp16OptimizerHook.py:123-141), so its Adam state['step'] does not
-// move there either — all without a host round trip.
-struct OptimState {
-    float coef;        // grad_scale * min(1, max_norm / (norm + 1e-6))
-    float bc1;         // 1 - beta1^t
-    float bc2_sqrt;    // sqrt(1 - beta2^t)
-    float norm;        // global gradient norm of this step (after grad_scale), for logging
-    int skip;          // 1: non-finite norm, leave parameters and moments alone
-    int t;             // Adam steps taken so far
-    int skipped;       // steps skipped so far
-    int pad;
-    // The loss scaler (fp16_utils.py:285-389 LossScaler), also on the device: the backward's root gradient is multiplied by
-    // loss_scale (read from here by the host graph), clv_optim_prep divides it out again and — in dynamic mode — moves it.
-    float loss_scale;      // current scale; 0: no scaler in use (the caller folds any static scale into grad_scale)
-    float scale_factor;    // dynamic: the factor the scale moves by (reference default 2)
-    int scale_window;      // dynamic: overflow-free iterations before the scale grows (reference default 1000)
-    int scale_iter;        // LossScaler.cur_iter
-    int last_overflow;     // LossScaler.last_overflow_iter (host initialises it to -1)
-    int dynamic;           // 1: LossScaler(mode='dynamic'); 0: static
-    int pad2[2];
-};
-
+// Device-resident optimizer state (optim_state.hpp): clv_optim_prep writes it, clv_adamw_step_dev reads it.
 __global__ void optim_prep_kernel(float* __restrict__ acc, OptimState* __restrict__ st, float beta1, float beta2,
                                   float max_norm, float grad_scale, float* __restrict__ slots) {
     // slots (clv_optim_prep_slots): the CLV_SUMSQ_SLOTS partial sums the weight-gradient kernels left (ssq_commit), one per
@@ -160,6 +138,7 @@ __global__ void optim_prep_kernel(float* __restrict__ acc, OptimState* __restric
     }
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     OptimState o = *st;
+    o.grad_loss_scale = o.loss_scale;                          // what THIS step's gradients carry (clv_grad_report), before it moves
     if (o.loss_scale > 0.f) grad_scale /= o.loss_scale;        // (a power of two unless the caller chose otherwise: exact)
     const float raw = acc[0] + extra;
     const float ss = raw * grad_scale * grad_scale;
@@ -302,7 +281,6 @@ extern "C" int clv_optim_prep(float* sumsq, void* state, float beta1, float beta
 extern "C" int clv_optim_prep_slots(float* sumsq, float* sumsq_slots, void* state, float beta1, float beta2,
                                     float max_norm, float grad_scale, void* stream) {
     if (!sumsq || !state || (((uintptr_t)state) & 3)) return CLV_ERR_ARG;
-    static_assert(sizeof(OptimState) == CLV_OPTIM_STATE_BYTES, "OptimState layout is part of the ABI");
     static_assert(CLV_SUMSQ_SLOTS == 64, "one slot per lane of the prep kernel's wave");
     hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, (OptimState*)state, beta1,
                        beta2, max_norm, grad_scale, sumsq_slots);

@@ -208,9 +208,16 @@ class _Segment:
 class CloverEngine:
     def __init__(self, model, sample_batch, lr=5e-5, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.005,
                  paramwise_cfg=None, grad_clip=15.0, max_iters=100000, warmup_iters=0, min_lr_ratio=1e-3,
-                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None, virtual_ranks=1):
+                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None, virtual_ranks=1, overflow_report=False):
         self.model = model
         self.virtual_ranks = int(virtual_ranks)
+        # overflow_report=True: every optimizer step also launches clv_grad_report in its "on skip" mode over the gradients —
+        # two kernels per slab that return at once unless the step was skipped; overflow_report() then names the
+        # parameters that held the non-finite values.  Off (the default): the step launches what it always launched.
+        self._overflow_report = bool(overflow_report)
+        self._report_tables = None             # per segment ops.GradReportTable, built on first use
+        self._report_out = None                # per segment: the report of the last skipped step (overflow_report=True)
+        self._stats_out = None                 # per segment: what grad_stats() writes
         # Loss scaling (mmcv_Fp16OptimizerHook.py:33-50,96-149; `fp16 = dict(loss_scale='dynamic')` in the headline config,
         # pretrain_webvid_cc3m.py:21).  `loss_scale` takes what the hook takes: a float (static), 'dynamic'
         # (LossScaler(mode='dynamic'): 2**32, factor 2, window 1000) or a dict of LossScaler arguments; None = the build's
@@ -345,6 +352,8 @@ class CloverEngine:
         self._prepacked = frozenset()
         self._setup_first_touch(sample_batch)
         self._setup_fused_norm()
+        if self._overflow_report:
+            self._report_out = [ops.grad_report_new(tab, device) for tab in self._grad_report_tables()]
 
     def _check_virtual_ranks(self, model, sample_batch):
         """What a virtual-rank step cannot reproduce is refused with its reason."""
@@ -1077,8 +1086,70 @@ class CloverEngine:
             ops.adamw_step_dev(seg.flat_p, g, seg.exp_avg, seg.exp_avg_sq, seg.shadow, self.optim_state,
                                lr * seg.lr_mult, self.betas[0], self.betas[1], self.eps, seg.weight_decay)
             seg.refresh_transposed()
+        if self._overflow_report:              # behind the skip decision, ahead of the clearing: the evidence is still there
+            for g, tab, out in zip(grads, self._grad_report_tables(), self._report_out):
+                ops.grad_report(g, tab, self.optim_state, out, 0)
         self.zero_grads()
         self.last_lr = lr
+
+    # ------------------------------------------------------------------ overflow report (csrc/grad_report.hip)
+    def _grad_report_tables(self):
+        """One clv_grad_report table per segment: every parameter's slab slot, phantom padding rows included (element
+        offsets: the same table reads the fp32 slab and its 16-bit wire copy)."""
+        if self._report_tables is None:
+            def scanned(p):
+                pad = getattr(p, '_clv_pad_grad', None)
+                return pad.numel() if pad is not None else p.numel()
+            self._report_tables = [ops.grad_report_table([(off, scanned(p)) for p, off in zip(sg.params, sg.offsets)],
+                                                         self._device) for sg in self.segments]
+        return self._report_tables
+
+    def _report_rows(self, outs, offending_only):
+        """Host side of a report (syncs): the segments' records as rows in TRUE gradient units."""
+        reps = [ops.grad_report_read(out, tab) for out, tab in zip(outs, self._grad_report_tables())]
+        head = reps[0]
+        if head['n_params'] == 0:              # the kernels never wrote it
+            return None
+        scale = head['loss_scale'] if head['loss_scale'] > 0.0 else 1.0
+        unit = 1.0 / (self.world * self.virtual_ranks) / scale
+        rows = []
+        for sg, rep in zip(self.segments, reps):
+            for name, p, nf, mx, ss in zip(sg.names, sg.params, rep['nonfinite'].tolist(), rep['max_abs'].tolist(),
+                                           rep['sumsq'].tolist()):
+                if nf or not offending_only:
+                    rows.append((name, p.numel(), int(nf), mx * unit, math.sqrt(ss) * unit))
+        return dict(t=head['t'], skipped=head['skipped'], loss_scale=scale, rows=rows)
+
+    def overflow_report(self):
+        """What the last SKIPPED optimizer step found in its gradients (host sync) — ``None`` if this engine has not skipped
+        a step yet, else ``dict(t, skipped, loss_scale, rows)``: Adam's step count and the count of skipped steps at that
+        moment, the loss scale those gradients carried, and one row ``(name, numel, nonfinite, max_abs, norm)`` per
+        parameter with a non-finite gradient element — ``max_abs`` and ``norm`` over the parameter's FINITE elements, in
+        true gradient units (the loss scale and the 1 / (world * virtual_ranks) averaging divided out).  Steps that were
+        taken leave it as it was.  Needs ``CloverEngine(..., overflow_report=True)``."""
+        if not self._overflow_report:
+            raise RuntimeError('overflow_report(): this engine was built without overflow_report=True, so its optimizer '
+                               'steps do not take the report; pass CloverEngine(..., overflow_report=True) (tools/train.py: '
+                               'the config key overflow_report = dict(interval=...))')
+        return self._report_rows(self._report_out, offending_only=True)
+
+    def grad_stats(self):
+        """The same rows for EVERY parameter of the gradients as they stand (host sync): call it between
+        ``finish_backward()`` and ``optimizer_step()``.  ``loss_scale`` is the scale of the backward that just ran."""
+        if self._stats_out is None:
+            self._stats_out = [ops.grad_report_new(tab, self._device) for tab in self._grad_report_tables()]
+        grads = self.wire if self.wire is not None else [seg.flat_g for seg in self.segments]
+        for g, tab, out in zip(grads, self._grad_report_tables(), self._stats_out):
+            ops.grad_report(g, tab, self.optim_state, out, 1)
+        return self._report_rows(self._stats_out, offending_only=False)
+
+    def step_stats(self):
+        """What a log line wants of the optimizer's device record, in ONE read (host sync): ``loss_scale`` of the next
+        backward (1.0 without a scaler), ``grad_norm`` of the last step (not finite when it was skipped), ``skipped`` and
+        ``t`` (steps skipped / taken so far), ``skip`` (1: the last step was skipped), ``calls`` (optimizer_step() calls)."""
+        st = ops.optim_state_read(self.optim_state)
+        return dict(loss_scale=st['loss_scale'] if self._scaler_on else 1.0, grad_norm=st['norm'], skipped=st['skipped'],
+                    t=st['t'], skip=st['skip'], calls=self.step_count)
 
     # ------------------------------------------------------------------ weight EMA (the reference's ema_hook)
     def ema_enable(self, skip_buffers=False):

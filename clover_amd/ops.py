@@ -2588,8 +2588,90 @@ def ema_swap(table):
         check(_lib.lib().clv_ema_swap(_ptr(table.swap), table.n_entries, table.n_blocks, _stream()), 'clv_ema_swap')
 
 
+# --------------------------------------------------------------------------- overflow report (csrc/grad_report.hip)
+GRAD_REPORT_HEADER_WORDS, GRAD_REPORT_STAT_WORDS = 8, 4      # include/clover_hip.h: CLV_GRAD_REPORT_HEADER_BYTES / _STAT_BYTES
+
+
+class GradReportTable(NamedTuple):
+    """Device table of clv_grad_report over the parameters of one gradient buffer (grad_report_table)."""
+    table: torch.Tensor                    # int64: n_params x {first chunk, chunks}, then n_chunks x {parameter, start, count}
+    n_params: int
+    n_chunks: int
+    extent: int                            # one past the last element a chunk covers: what a buffer must hold at least
+    numels: tuple                          # elements per parameter
+    numel: int                             # ... of all of them
+
+
+def grad_report_chunks(params_offsets):
+    """The host half of grad_report_table.  ``params_offsets``: one (offset, numel) pair per parameter, in elements of the
+    buffer.  -> (rows {first chunk, chunks} per parameter, rows {parameter, start, count} per chunk): every parameter cut
+    into chunks of <= SUMSQ_CHUNK elements, its chunks adjacent and in order; an empty parameter has none."""
+    prows, crows = [], []
+    for i, (off, n) in enumerate(params_offsets):
+        off, n = int(off), int(n)
+        if off < 0 or n < 0 or n >= 2 ** 31:
+            raise ValueError(f'grad_report_table: parameter {i}: offset {off}, numel {n} (need offset >= 0, 0 <= numel < 2^31)')
+        prows.append((len(crows), (n + SUMSQ_CHUNK - 1) // SUMSQ_CHUNK))
+        crows += [(i, off + a, min(SUMSQ_CHUNK, n - a)) for a in range(0, n, SUMSQ_CHUNK)]
+    return prows, crows
+
+
+def grad_report_table(params_offsets, device):
+    """Table for grad_report over one gradient buffer (an fp32 slab or its 16-bit wire copy: the offsets are elements, so one
+    table serves both).  Offsets of any alignment are legal; 8-element aligned ones, as the slabs lay parameters out, put
+    every chunk on a 16-byte boundary."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('clover_amd ops run only on a HIP device (MI355X); there is no CPU fallback — '
+                           'got device %s' % device)
+    prows, crows = grad_report_chunks(params_offsets)
+    flat = [v for r in prows for v in r] + [v for r in crows for v in r]
+    t = torch.tensor(flat if flat else [0], dtype=torch.int64).to(device)
+    return GradReportTable(t, len(prows), len(crows), max((s + c for _, s, c in crows), default=0),
+                           tuple(int(n) for _, n in params_offsets), sum(int(n) for _, n in params_offsets))
+
+
+def grad_report_new(table, device):
+    """A zeroed report buffer for ``table`` (int32 words: header, one record per parameter, one per chunk)."""
+    words = GRAD_REPORT_HEADER_WORDS + GRAD_REPORT_STAT_WORDS * (table.n_params + table.n_chunks)
+    return torch.zeros(words, dtype=torch.int32, device=device)
+
+
+def grad_report(buf, table, state, out, mode):
+    """Per-parameter {non-finite count, largest finite |g|, sum of squares of the finite g} of the gradient buffer ``buf``
+    (fp32, or the 16-bit storage type) into ``out``: two launches on the current stream, no host sync, capturable.
+    ``mode`` 0: only when ``state`` says the step was skipped — otherwise both kernels return at once and ``out`` keeps the
+    last skipped step's report; 1: always."""
+    _need_gpu(buf, table.table, state, out)
+    if buf.dtype not in (torch.float32, BF16) or not buf.is_contiguous():
+        raise ValueError(f'grad_report: buf must be a contiguous fp32 or {BF16} tensor, got {buf.dtype}')
+    if buf.numel() < table.extent:
+        raise ValueError(f'grad_report: the table covers {table.extent} elements, buf holds {buf.numel()}')
+    words = GRAD_REPORT_HEADER_WORDS + GRAD_REPORT_STAT_WORDS * (table.n_params + table.n_chunks)
+    if out.dtype != torch.int32 or out.numel() < words or not out.is_contiguous():
+        raise ValueError(f'grad_report: out must be a contiguous int32 tensor of >= {words} words (grad_report_new)')
+    if state.dtype != torch.int32 or state.numel() * 4 < OPTIM_STATE_BYTES:
+        raise ValueError('grad_report: state is the int32 record of optim_state_new')
+    if mode not in (0, 1):
+        raise ValueError(f'grad_report: mode is 0 (on skip) or 1 (always), got {mode!r}')
+    gbytes = 2 if buf.dtype == BF16 else 4
+    with _Timed('grad_report_kernel', 3 * table.numel, gbytes * table.numel):
+        check(_lib.lib().clv_grad_report(_ptr(buf), 1 if buf.dtype == BF16 else 0, _ptr(table.table), table.n_params,
+                                         table.n_chunks, _ptr(state), _ptr(out), int(mode), _stream()), 'clv_grad_report')
+
+
+def grad_report_read(out, table):
+    """Host copy of a report (syncs): dict(t, skipped, loss_scale, n_params, nonfinite, max_abs, sumsq, norm), the last four
+    one CPU tensor each with one entry per parameter, in the buffer's units.  n_params == 0: no call has reported yet."""
+    raw = out.detach().cpu()
+    f = raw.view(torch.float32)
+    a, b = GRAD_REPORT_HEADER_WORDS, GRAD_REPORT_HEADER_WORDS + GRAD_REPORT_STAT_WORDS * table.n_params
+    return dict(t=int(raw[0]), skipped=int(raw[1]), loss_scale=float(f[2]), n_params=int(raw[3]), nonfinite=raw[a:b:4].clone(),
+                max_abs=f[a + 1:b:4].clone(), sumsq=f[a + 2:b:4].clone(), norm=f[a + 3:b:4].clone())
+
+
 # --------------------------------------------------------------------------- video QA / fill-in-the-blank (csrc/qa.hip)
-QA_MASK_ID = 103          # BERT [MASK]: the answer row of fill-in-the-blank (multimodal_transformer_finetune.py:100-102)
+QA_MASK_ID = 103         # BERT [MASK]: the answer row of fill-in-the-blank (multimodal_transformer_finetune.py:100-102)
 
 
 def qa_answer_rows(token_ids, seq_len, base, answer_mask, mask_id=QA_MASK_ID):

@@ -215,6 +215,70 @@ class LogHook(Hook):
                 self.printer(rec)
 
 
+class OverflowHook(Hook):
+    """What mmcv prints on every fp16 log line and what ``Fp16OptimizerHook`` warns about (mmcv_Fp16OptimizerHook.py:123-141),
+    for an engine whose loss scaler, overflow test and skip decision never leave the device.
+
+    Every ``interval`` optimizer steps ONE read of the engine's optimizer record (``engine.step_stats()``, a host sync)
+    gives a record ``dict(epoch, iter, loss_scale, grad_norm, skipped)`` (``records``).  If ``skipped`` grew since the last
+    look, the engine's overflow report (``engine.overflow_report()``: needs ``CloverEngine(overflow_report=True)``) is
+    printed: the ``top`` parameters by count of non-finite gradient elements, then by largest finite magnitude.  With
+    ``max_consecutive_skips = N`` a run of N skipped steps in a row raises ``RuntimeError`` with the scale and those
+    parameters — a static scale that overflows skips every step from then on, and says nothing.  The run is derived from the
+    ``skipped`` and ``calls`` deltas between two looks: every step of the window skipped extends it, none skipped ends it;
+    a window with both (possible with ``interval > 1`` only) restarts it from what is known, the last step."""
+
+    def __init__(self, interval=10, top=5, max_consecutive_skips=None, printer=None):
+        assert interval >= 1 and top >= 1 and (max_consecutive_skips is None or max_consecutive_skips >= 1)
+        self.interval, self.top, self.max_consecutive_skips = interval, top, max_consecutive_skips
+        self.printer = print if printer is None else printer
+        self.records, self.run_of_skips = [], 0
+        self._steps, self._last = 0, None
+
+    def before_run(self, runner):
+        eng = runner.stepper
+        missing = [a for a in ('step_stats', 'overflow_report') if not hasattr(eng, a)]
+        if missing:
+            raise TypeError(f'{type(self).__name__}: the skip decision lives in the CloverEngine; the stepper '
+                            f'{type(eng).__name__} has no {", ".join(missing)} — drive the run with a CloverEngine')
+        self._last = eng.step_stats()
+
+    @staticmethod
+    def top_rows(report, top):
+        return sorted(report['rows'], key=lambda r: (-r[2], -r[3]))[:top]
+
+    def describe(self, report):
+        rows = self.top_rows(report, self.top)
+        lines = [f'overflow: step skipped ({report["skipped"]} so far, {report["t"]} taken) at loss_scale '
+                 f'{report["loss_scale"]:g}; {len(report["rows"])} parameter(s) with non-finite gradients, top {len(rows)}:']
+        lines += [f'  {name}: {nf} of {numel} non-finite, max |g| {mx:.4g}, norm {norm:.4g} over the finite ones'
+                  for name, numel, nf, mx, norm in rows]
+        return '\n'.join(lines)
+
+    def after_train_iter(self, runner):
+        self._steps += 1
+        if self._steps % self.interval != 0:
+            return
+        eng = runner.stepper
+        st, last = eng.step_stats(), self._last
+        self._last = st
+        self.records.append(dict(epoch=runner.epoch + 1, iter=runner.inner_iter + 1, loss_scale=st['loss_scale'],
+                                 grad_norm=st['grad_norm'], skipped=st['skipped']))
+        d_skipped, d_calls = st['skipped'] - last['skipped'], st['calls'] - last['calls']
+        if d_skipped <= 0:
+            self.run_of_skips = 0
+            return
+        self.run_of_skips = self.run_of_skips + d_skipped if d_skipped == d_calls else int(bool(st.get('skip', 0)))
+        report = eng.overflow_report()
+        if report is not None:
+            self.printer(self.describe(report))
+        if self.max_consecutive_skips is not None and self.run_of_skips >= self.max_consecutive_skips:
+            names = ', '.join(r[0] for r in self.top_rows(report, self.top)) if report else 'no report'
+            raise RuntimeError(f'{self.run_of_skips} optimizer steps in a row were skipped for non-finite gradients at '
+                               f'loss_scale {st["loss_scale"]:g} (max_consecutive_skips={self.max_consecutive_skips}); '
+                               f'parameters with non-finite gradients: {names}')
+
+
 class CheckpointHook(Hook):
     def __init__(self, out_dir, interval=1):
         self.out_dir, self.interval = out_dir, interval

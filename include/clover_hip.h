@@ -534,7 +534,8 @@ int clv_transpose_batch(const void* src_base, void* dst_base, const void* table,
                         int32_t total_tiles, void* stream);
 
 /* The same step with the optimizer's scalars held on the DEVICE (no host sync, hipGraph-safe):
- * state = CLV_OPTIM_STATE_BYTES bytes {float coef, bc1, bc2_sqrt, norm; int32 skip, t, skipped, pad; float loss_scale,
+ * state = CLV_OPTIM_STATE_BYTES bytes {float coef, bc1, bc2_sqrt, norm; int32 skip, t, skipped; float grad_loss_scale (the
+ * loss_scale of the last prep's gradients, for clv_grad_report; padding before it existed); float loss_scale,
  * scale_factor; int32 scale_window, scale_iter, last_overflow, dynamic, pad, pad}, zeroed once by the caller.  The second
  * half is the reference's LossScaler (mmaction/core/hooks/fp16_utils.py:285-389) held on the device: with loss_scale > 0
  * the caller multiplies the root gradient of its backward by state.loss_scale (a device read: it stays inside a hipGraph),
@@ -578,6 +579,37 @@ int clv_adamw_step_dev(float* p, const float* g, float* m, float* v, void* shado
 #define CLV_EMA_BLOCK_BYTES 16
 int clv_ema_update(const void* table, int32_t n_entries, int32_t n_blocks, double momentum, void* stream);
 int clv_ema_swap(const void* table, int32_t n_entries, int32_t n_blocks, void* stream);
+
+/* ------------------------------------------------------------------ overflow report (csrc/grad_report.hip)
+ * Which parameters hold the non-finite gradients behind a skipped step.  The reference asks every parameter in turn, with a
+ * host synchronisation each (LossScaler.has_overflow / _has_inf_or_nan, mmaction/core/hooks/fp16_utils.py:328-349), and
+ * its hook announces every overflow (mmcv_Fp16OptimizerHook.py:123-141); here the skip decision is on the device
+ * (clv_optim_prep), so the report is taken there as well: two launches over ONE gradient buffer that return at once unless
+ * state.skip is set.
+ *   buf    the gradients: elem = CLV_GRAD_REPORT_F32 fp32 (a slab), CLV_GRAD_REPORT_HALF the library's 16-bit element type
+ *          (the wire copy of a data-parallel job); naturally aligned
+ *   table  (8-byte aligned) n_params x {int64 first_chunk, n_chunks_of_it}, then n_chunks x {int64 parameter, start, count}:
+ *          the caller cuts every parameter into chunks of 1 .. CLV_SUMSQ_CHUNK elements (start in elements from buf), the
+ *          chunks of one parameter adjacent and in order; every chunk is one 256-thread block
+ *   state  the CLV_OPTIM_STATE_BYTES record of clv_optim_prep.  Its former padding word behind `skipped` now holds the
+ *          loss_scale the gradients of the last clv_optim_prep carried (a dynamic scale has moved by the time skip is known)
+ *   report (16-byte aligned) CLV_GRAD_REPORT_HEADER_BYTES + (n_params + n_chunks) * CLV_GRAD_REPORT_STAT_BYTES bytes:
+ *          {int32 t, skipped; float loss_scale; int32 n_params; 4 x int32 0}, then per parameter, then per chunk (scratch)
+ *          {int32 nonfinite; float max_abs, sumsq, norm}: the count of NaN / infinite elements, and over the FINITE ones the
+ *          largest magnitude, the fp32 sum of squares and its square root, all in the buffer's units (loss scale included)
+ *   mode   0: "on skip" — every block reads state.skip first and returns when it is 0, leaving the report of the last
+ *          skipped step readable; loss_scale = the one those gradients carried.  1: always; loss_scale = state.loss_scale
+ *          (for use BEFORE clv_optim_prep)
+ * 16-byte loads wherever a chunk allows, fixed-order reductions, no atomics: the report is a pure function of buffer and
+ * table, bit-reproducible, rewritten whole by every reporting call.  Plain launches on `stream`; capturable. */
+#define CLV_GRAD_REPORT_F32 0
+#define CLV_GRAD_REPORT_HALF 1
+#define CLV_GRAD_REPORT_PARAM_BYTES 16
+#define CLV_GRAD_REPORT_CHUNK_BYTES 24
+#define CLV_GRAD_REPORT_HEADER_BYTES 32
+#define CLV_GRAD_REPORT_STAT_BYTES 16
+int clv_grad_report(const void* buf, int32_t elem, const void* table, int32_t n_params, int32_t n_chunks,
+                    const void* state, void* report, int32_t mode, void* stream);
 
 /* ------------------------------------------------------------------ parity mode (fp32 storage + fp32 arithmetic)
  * The reference's CPU path is fp32 (north_star: "match the reference mmaction CPU path ... losses within 1e-3").  The

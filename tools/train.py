@@ -3,6 +3,7 @@
 
     python tools/train.py configs/pretrain_synthetic.py --launcher none --cfg-options total_epochs=1
     python -m torch.distributed.run --nproc-per-node 8 tools/train.py configs/pretrain_synthetic.py --launcher pytorch
+    python tools/train.py configs/pretrain_overflow_report_synthetic.py --launcher none     # names what a skipped step overflowed in
 
 Same config format (`_base_`, `model = dict(type='CloverPretrain', ...)`, `optimizer` with `base_lr`, `lr_config`,
 `total_epochs`, `workflow`, `checkpoint_config`, `log_config`), same CLI names.  The dataset side (decoding,
@@ -64,7 +65,18 @@ def engine_kwargs(cfg, lr, half_f16=True):
                 # device-resident loss scaler (fp16 build; the bf16 build keeps its default: none)
                 loss_scale=(cfg.get('fp16') or {}).get('loss_scale') if half_f16 else None,
                 # `virtual_ranks = k`: every optimizer step takes k batches whose contrastive losses see all k * B rows
-                virtual_ranks=int(cfg.get('virtual_ranks', 1) or 1))
+                virtual_ranks=int(cfg.get('virtual_ranks', 1) or 1),
+                # `overflow_report = dict(interval=...)`: skipped steps leave a per-parameter report (overflow_hook below)
+                overflow_report=bool(cfg.get('overflow_report')))
+
+
+def overflow_hook(cfg, rank=0):
+    """The OverflowHook a config's top-level `overflow_report = dict(interval=..., top=..., max_consecutive_skips=...)` asks
+    for, or None without the key.  Every rank gets one (a run of skipped steps must stop them all); rank 0 prints."""
+    if not cfg.get('overflow_report'):
+        return None
+    from clover_amd.runner import OverflowHook
+    return OverflowHook(printer=print if rank == 0 else (lambda text: None), **dict(cfg.overflow_report))
 
 
 def main():
@@ -123,6 +135,8 @@ def main():
         runner.register_hook(LogHook(cfg.get('log_config', {}).get('interval', 10), printer=print))
         if cfg.get('checkpoint_config'):
             runner.register_hook(CheckpointHook(cfg.work_dir, cfg.checkpoint_config.get('interval', 1)))
+    if overflow_hook(cfg, rank) is not None:
+        runner.register_hook(overflow_hook(cfg, rank))
     if args.validate:                                    # tools/train.py:192-209 — on EVERY rank: the collection is a collective
         from clover_amd.utils.synthetic_loaders import SyntheticTestLoader
         ev = dict(cfg.get('evaluation') or {})
