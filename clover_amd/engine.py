@@ -20,6 +20,7 @@ DefaultOptimizerConstructor + AdamW (pretrain_webvid_cc3m.py:129-137), Fp16Optim
 * ``ema_enable`` / ``ema_update`` / ``ema_swap``: the reference's ``ema_hook`` (mmaction/core/hooks/ema.py) — an fp32 moving
   average of the weights in a slab of its own per segment, updated and exchanged with the weights by one HIP launch each.
 """
+import inspect
 import math
 
 import os
@@ -205,6 +206,39 @@ class _Segment:
         return f
 
 
+def _complement(spans, total):
+    """The ranges of [0, total) that the sorted (begin, end) ``spans`` leave out, in order and none of them empty; spans
+    may touch or overlap.  Spans and ranges together tile [0, total)."""
+    ranges, pos = [], 0
+    for a, b in spans:
+        if a > pos:
+            ranges.append((pos, a))
+        pos = max(pos, b)
+    if pos < total:
+        ranges.append((pos, total))
+    return ranges
+
+
+class _Capture:
+    """The captured step of ONE batch geometry: its hipGraphs and the static tensors they read and write.  capture()
+    builds it as a local object and publishes it whole (``engine._captures[sig]``, then ``_activate``); everything of
+    the active geometry but the assignable ``engine.graph`` is reached through ``engine._active``."""
+    __slots__ = ('graph', 'graph_bwd', 'graph_bwd_video', 'graph_bwd_text', 'graph_loss', 'loss_io', 'batch', 'emb',
+                 'mlm', 'demb', 'dmlm', 'cuts', 'stale_views', 'prepacked')
+
+    def __init__(self, graph, graph_bwd, graph_bwd_video, graph_bwd_text, batch, emb, mlm, demb, dmlm, cuts,
+                 stale_views, prepacked):
+        self.graph, self.graph_bwd = graph, graph_bwd          # encode, and its backward from d emb / d mlm down
+        self.graph_bwd_video = graph_bwd_video                 # data-parallel: the video encoder's cut graphs, else None
+        self.graph_bwd_text = graph_bwd_text                   # ... and the text encoder's, or None
+        self.graph_loss, self.loss_io = None, None             # the loss section as a graph (_capture_loss_graph), or None
+        self.batch = batch                                     # static inputs
+        self.emb, self.mlm, self.demb, self.dmlm = emb, mlm, demb, dmlm
+        self.cuts = cuts                                       # the cut leaves (kept alive with the graphs)
+        self.stale_views = stale_views                         # first-touch slots this geometry's backward never writes
+        self.prepacked = prepacked                             # buckets whose wire copy the backward graphs write
+
+
 class CloverEngine:
     def __init__(self, model, sample_batch, lr=5e-5, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.005,
                  paramwise_cfg=None, grad_clip=15.0, max_iters=100000, warmup_iters=0, min_lr_ratio=1e-3,
@@ -248,14 +282,28 @@ class CloverEngine:
         self._stale_cleared = False            # finish_backward() cleared the unreached first-touch slots of this step
         self.lr_iter = 0                       # index into the LR schedule when no runner drives it (set_lr)
         self._lr_external = None
-        self.graph = None
-        self.graph_bwd_video = None
-        self.graph_bwd_text = None
-        self._captures = {}                    # batch-shape signature -> the captured graphs + their static tensors
+        self.last_lr = None                    # what the last optimizer_step() used
+        self.graph = None                      # None: the step runs eagerly; else the forward graph step() replays
+        self._captures = {}                    # batch-shape signature -> its _Capture
+        self._active, self._active_sig = None, None        # the selected _Capture (also while ``graph`` is None)
+        self._bwd_text_stream = None           # data-parallel: the stream the text encoder's backward graph replays on
         self._ema_table = None                 # ops.EmaTable once ema_enable() ran
+        self._ema_skip_buffers = False
         self.ema_names = {}                    # state_dict name -> its ``ema_*`` buffer name
         self.ema_swapped = False               # True: the parameters hold the average, the ``ema_*`` buffers the weights
-        self._active_sig = None
+        self._vr_emb, self._vr_emb_recomputed = None, {}   # virtual ranks: the last step's stashed embeddings
+        self._vr_keep_recomputed = False       # tests: keep the embeddings the recomputed forwards produce
+        self._one = None                       # cached root gradient of an unscaled loss
+        # Phase clock of the graphed step (bench.py --phases): events on the main stream at the phase boundaries — the
+        # forward graph, the eager loss section, the backward graphs, reducer.finish() + optimizer.  GPU time between
+        # consecutive marks, averaged by phase_ms(); off (None) unless start_phase_timing() was called.
+        self._phase_ev = None
+        # the recognizer names the batch entries its rank-local part consumes (CloverPretrain: captions + both
+        # masks; CloverFinetune retrieval: captions only)
+        self._encode_keys = tuple(getattr(model, 'CLV_ENCODE_KEYS', ('token_ids', 'input_mask', 'mlm_label', 'v_token_mask')))
+        self._loss_takes_gathered = (hasattr(model, 'contrastive_losses')
+                                     and 'gathered' in inspect.signature(model.contrastive_losses).parameters)
+        self._encode_takes_text_cut = hasattr(model, 'encode') and 'text_cut' in inspect.signature(model.encode).parameters
         device = next(model.parameters()).device
         if device.type != 'cuda':
             raise RuntimeError('CloverEngine drives the HIP kernels: move the model to an MI355X first (there is no '
@@ -348,8 +396,9 @@ class CloverEngine:
         for seg in self.segments:
             seg.build_transposed()
         self._zero_views = None                # None: clear whole slabs
-        self._stale_views = []
-        self._prepacked = frozenset()
+        self._fresh_sinks = {}                 # id(sink) -> (sink, segment index, slab offset, numel) of the first-touch slots
+        self._ft, self.first_touch_params = ops.FirstTouch(), 0
+        self._norm_state = ops.FusedNormState()
         self._setup_first_touch(sample_batch)
         self._setup_fused_norm()
         if self._overflow_report:
@@ -382,7 +431,7 @@ class CloverEngine:
         fold launches, an explicit pass on any other path), so the norm pass before the clip reads only the REST of the
         slabs — `clv_sumsq_ranges` over the complement — instead of all 0.76 GB.  Not in data-parallel jobs: their norm is
         that of the REDUCED gradients (mmcv_Fp16OptimizerHook.py:119-131).  CLOVER_FUSED_NORM=0 switches it off."""
-        fresh = getattr(self, '_fresh_sinks', None)
+        fresh = self._fresh_sinks
         if (not fresh or self.reducer.active or self.wire is not None or os.environ.get('CLOVER_FUSED_NORM', '1') != '1'
                 or not self.segments[0].flat_g.is_cuda or self.virtual_ranks > 1):
             return
@@ -390,15 +439,7 @@ class CloverEngine:
         tables = []
         for si, seg in enumerate(self.segments):
             spans = sorted((off, off + n) for _, sj, off, n in fresh.values() if sj == si)
-            ranges, pos = [], 0
-            for a, b in spans:
-                if a > pos:
-                    ranges.append((pos, a))
-                pos = max(pos, b)
-            if pos < seg.flat_g.numel():
-                ranges.append((pos, seg.flat_g.numel()))
-            tables.append(ops.sumsq_range_table(ranges, seg.flat_g.device))
-        self._norm_state = ops.FusedNormState()
+            tables.append(ops.sumsq_range_table(_complement(spans, seg.flat_g.numel()), seg.flat_g.device))
         for sk, _, _, _ in fresh.values():
             sk._clv_ssq = ops.NormSlots(self.sumsq, slots, self._norm_state)
         self._norm_tables = tables
@@ -413,8 +454,6 @@ class CloverEngine:
         first-touch; a slot qualifies when it comes out finite and equal to the reference (a gradient that also arrives
         through autograd BEFORE its launch, or a sink the launch does not recognise, fails here and keeps being cleared).
         A third pass with the final marking must reproduce every gradient, otherwise the scheme is switched off."""
-        self._ft = ops.FirstTouch()
-        self.first_touch_params = 0
         if os.environ.get('CLOVER_GRAD_FIRST_TOUCH', '1') != '1' or self.virtual_ranks > 1:
             return                             # (virtual ranks: k backward passes ADD into the slabs, nothing may store)
         sinks = {}                             # data_ptr -> (sink tensor, segment index, slab offset, numel)
@@ -479,8 +518,7 @@ class CloverEngine:
             torch.cuda.set_rng_state(gpu_rng)
             drop_ctr.copy_(drop_ctr0)
         mark(ok)
-        for seg in self.segments:
-            seg.flat_g.zero_()
+        self._clear_all()
         if not ok:
             return
         # what is still cleared every step: the complement of the first-touch slots, as few contiguous views as possible
@@ -488,14 +526,17 @@ class CloverEngine:
         self._zero_views = []
         for si, seg in enumerate(self.segments):
             spans = sorted((off, off + n) for _, sj, off, n in self._fresh_sinks.values() if sj == si)
-            pos = 0
-            for a, b in spans:
-                if a > pos:
-                    self._zero_views.append(seg.flat_g[pos:a])
-                pos = max(pos, b)
-            if pos < seg.flat_g.numel():
-                self._zero_views.append(seg.flat_g[pos:])
+            self._zero_views += [seg.flat_g[a:b] for a, b in _complement(spans, seg.flat_g.numel())]
         self.first_touch_params = sum(n for _, _, _, n in self._fresh_sinks.values())
+
+    def _clear_all(self):
+        """All gradients and norm partial sums clear, every first-touch slot stale: what a fresh step starts from.  For
+        set-up, dry_step() and capture(); between steps zero_grads() clears only what needs it."""
+        for seg in self.segments:
+            seg.flat_g.zero_()
+        self.sumsq.zero_()
+        self._norm_state.dirty = False
+        self._ft.done.clear()
 
     def zero_grads(self):
         """Clear the gradients for the next backward: zero-fill what accumulates, mark the first-touch slots stale."""
@@ -504,7 +545,7 @@ class CloverEngine:
             for seg in self.segments:
                 seg.flat_g.zero_()
             return
-        views = self._zero_views + self._stale_views
+        views = self._zero_views + (self._active.stale_views if self._active is not None else [])
         if self._norm_tables is not None:
             views = views + [self.sumsq]       # a backward without an optimizer step (dry run, warm-up) left partial sums
         if views:
@@ -542,32 +583,33 @@ class CloverEngine:
         self._backward(lambda: out['loss'].backward())
         self.finish_backward()
         self._stale_cleared = False
-        for seg in self.segments:
-            seg.flat_g.zero_()
-        self.sumsq.zero_()
-        if self._norm_tables is not None:
-            self._norm_state.dirty = False
-        self._ft.done.clear()
+        self._clear_all()
         return out
 
     def step(self, batch):
         """forward + backward + gradient all-reduce + clip + AdamW.  Returns train_step's dict.  With ``virtual_ranks=k``
         ``batch`` is a sequence of k micro-batches of one geometry (forward_backward)."""
         self._refuse_swapped('step')
-        if self.virtual_ranks > 1:
-            out = self.forward_backward(batch)
-            self.optimizer_step()
-            return out
+        out = self.forward_backward(batch)
+        self.optimizer_step()
+        self._mark('optimizer')
+        return out
+
+    def _select(self, batch):
+        """Make the captured step of ``batch``'s geometry the active one.  The reference alternates 8-frame video and
+        1-frame image batches (clover_runner.py:76-93): one set of graphs per geometry, captured on first sight."""
+        sig = self._signature(batch)
+        if sig != self._active_sig:
+            if sig in self._captures:
+                self._activate(sig)
+            else:
+                self.capture(batch)
+
+    def _forward_backward_one(self, batch):
+        """Forward and backward of a single batch, graphed or eager, up to and including finish_backward()."""
         self.reducer.begin_step()
         if self.graph is not None:
-            sig = self._signature(batch)
-            if sig != self._active_sig:
-                # a different batch geometry (the reference alternates 8-frame video and 1-frame image batches,
-                # clover_runner.py:76-93): one set of graphs per geometry, captured on first sight
-                if sig in self._captures:
-                    self._activate(sig)
-                else:
-                    self.capture(batch)
+            self._select(batch)
             out = self._graphed_forward_backward(batch)
         else:
             self.reducer.prepacked = frozenset()
@@ -575,8 +617,6 @@ class CloverEngine:
             out = self.model.train_step(batch, None)
             self._backward(lambda: out['loss'].backward())
         self.finish_backward()
-        self.optimizer_step()
-        self._mark('optimizer')
         return out
 
     # ------------------------------------------------------------------ virtual ranks
@@ -602,23 +642,7 @@ class CloverEngine:
         ``num_samples`` counts the k B samples of the step."""
         self._refuse_swapped('forward_backward')
         if self.virtual_ranks == 1:
-            batch = batches if isinstance(batches, dict) else batches[0]
-            self.reducer.begin_step()
-            if self.graph is not None:
-                sig = self._signature(batch)
-                if sig != self._active_sig:
-                    if sig in self._captures:
-                        self._activate(sig)
-                    else:
-                        self.capture(batch)
-                out = self._graphed_forward_backward(batch)
-            else:
-                self.reducer.prepacked = frozenset()
-                self._ft.done.clear()
-                out = self.model.train_step(batch, None)
-                self._backward(lambda: out['loss'].backward())
-            self.finish_backward()
-            return out
+            return self._forward_backward_one(batches if isinstance(batches, dict) else batches[0])
         k = self.virtual_ranks
         if isinstance(batches, dict) or len(batches) != k:
             raise ValueError(f'virtual_ranks={k}: a step takes a sequence of {k} micro-batches, got '
@@ -631,13 +655,9 @@ class CloverEngine:
         self.reducer.begin_step()
         self.reducer.prepacked = frozenset()
         graphed = self.graph is not None
-        if graphed and sig != self._active_sig:
-            if sig in self._captures:
-                self._activate(sig)
-            else:
-                self.capture(batches[0])
-        model = self.model
-        keys = tuple(getattr(model, 'CLV_ENCODE_KEYS', ('token_ids', 'input_mask', 'mlm_label', 'v_token_mask')))
+        if graphed:
+            self._select(batches[0])
+        model, cap = self.model, self._active
         drop_ctr = ops._dropout_counter(self._device)
 
         def rng_save():
@@ -651,19 +671,19 @@ class CloverEngine:
             """encode of micro-batch j -> (emb, mlm): the static outputs of the forward graph, or eager tensors."""
             b = batches[j]
             if graphed:
-                for name, v in self._static_batch.items():
+                for name, v in cap.batch.items():
                     if b[name] is not v:
                         v.copy_(b[name], non_blocking=True)
                 self.graph.replay()
-                return self._static_emb, self._static_mlm
+                return cap.emb, cap.mlm
             with torch.enable_grad() if grad else torch.no_grad():
-                return model.encode(b['imgs'], **{name: b[name] for name in keys})
+                return model.encode(b['imgs'], **{name: b[name] for name in self._encode_keys})
 
         def backward(live, demb, dmlm):
             if graphed:
-                self._static_demb.copy_(demb)
-                if self._static_dmlm is not None:
-                    self._static_dmlm.copy_(dmlm)
+                cap.demb.copy_(demb)
+                if cap.dmlm is not None:
+                    cap.dmlm.copy_(dmlm)
                 self._replay_backward()
             else:
                 emb, mlm = live
@@ -686,8 +706,7 @@ class CloverEngine:
         # ---- the loss section, once, on all k * B rows
         E = torch.cat(embs, 0).requires_grad_()
         mlm = torch.stack(mlms).mean().requires_grad_() if mlms else None     # rank 0 logs the mean of the k local values
-        import inspect
-        if 'gathered' in inspect.signature(model.contrastive_losses).parameters:
+        if self._loss_takes_gathered:
             losses = model.contrastive_losses(None, mlm, gathered=E)
         else:
             losses = model.contrastive_losses(E, mlm)
@@ -710,14 +729,12 @@ class CloverEngine:
         self.finish_backward()
         return dict(loss=loss.detach(), log_vars=log_vars, num_samples=k * len(next(iter(batches[0].values()))))
 
-    _vr_keep_recomputed = False                # tests: keep the embeddings the recomputed forwards produce (_vr_emb_recomputed)
-
     def finish_backward(self):
         """Close a backward pass: clear the first-touch slots an EAGER backward did not reach, THEN complete the gradient
         exchange.  The order matters in data-parallel mode: ``reducer.finish()`` packs and all-reduces the
         bucket of an unreached parameter, and the norm / AdamW kernels read the reduced wire copy — a slot cleared after
         the exchange would still update the weight with the previous step's gradient.  (A captured geometry's unreached
-        slots are cleared with the rest of the gradients after every optimizer step: ``_stale_views``.)  A caller that
+        slots are cleared with the rest of the gradients after every optimizer step: ``stale_views``.)  A caller that
         drives its own ``loss.backward()`` calls this instead of ``reducer.finish()``."""
         if self.graph is None:
             stale = self._stale_sinks()
@@ -737,8 +754,6 @@ class CloverEngine:
                 run()
 
     # ------------------------------------------------------------------ hipGraph mode
-    _one = None
-
     def _parse_root_scaled(self, losses, **kw):
         """model._parse_losses for a backward the engine starts itself: the loss scale is handed to autograd as the ROOT
         gradient (_root_gradient) instead of through the recognizer's scaling node — one dependent launch less on the
@@ -758,49 +773,45 @@ class CloverEngine:
             self._one = torch.ones_like(loss)
         return self._one
 
-    _CAPTURE_FIELDS = ('graph', 'graph_bwd', 'graph_bwd_video', 'graph_bwd_text', '_static_batch', '_static_emb',
-                       '_static_mlm', '_static_demb', '_static_dmlm', '_static_cuts', 'graph_loss', '_loss_io',
-                       '_stale_views', '_prepacked')
-
     @staticmethod
     def _signature(batch):
         return tuple((k, tuple(v.shape)) for k, v in sorted(batch.items()))
 
     def _activate(self, sig):
-        for f, v in zip(self._CAPTURE_FIELDS, self._captures[sig]):
-            setattr(self, f, v)
-        self._active_sig = sig
+        cap = self._active = self._captures[sig]
+        self._active_sig, self.graph = sig, cap.graph
         # The previous optimizer step cleared the stale views of the geometry that ran THEN.  A first-touch slot that
         # geometry writes and this one never does still holds that step's gradient: clear this geometry's stale slots
         # before its first replay (afterwards zero_grads() keeps them clear while it stays active).
-        if self._stale_views:
-            torch._foreach_zero_(self._stale_views)
+        if cap.stale_views:
+            torch._foreach_zero_(cap.stale_views)
 
     def input_buffers(self):
         """The static input tensors of the active hipGraphs (None before capture): a loader that writes its host-to-device
         copies straight into them — and hands the same dict to step() — saves the per-step staging copy."""
-        return self._static_batch if self.graph is not None else None
+        return self._active.batch if self.graph is not None else None
 
     def _graphed_forward_backward(self, batch):
         """encode (hipGraph) -> gather + contrastive losses (eager: it holds the step's only forward
         collective) -> backward of the losses (eager, a handful of kernels) -> encode backward (hipGraph)."""
-        for k, v in self._static_batch.items():
+        cap = self._active
+        for k, v in cap.batch.items():
             if batch[k] is not v:
                 v.copy_(batch[k], non_blocking=True)
         self._mark('start')
         self.graph.replay()
         self._mark('forward')
-        if getattr(self, 'graph_loss', None) is not None:
+        if cap.graph_loss is not None:
             # the loss section as a graph of its own: only the feature all-gather (and the all-reduce of the logged
             # scalars) stay eager — ~60 launch-bound kernels otherwise paced by the host
-            g_static, names, packed, loss = self._loss_io
+            g_static, names, packed, loss = cap.loss_io
             with torch.no_grad():
                 if collectives_active():
                     from .utils.gather_loss import gather_rows
-                    g_static.copy_(gather_rows(self._static_emb.float(), equal_sizes=True))
+                    g_static.copy_(gather_rows(cap.emb.float(), equal_sizes=True))
                 else:
-                    g_static.copy_(self._static_emb)
-            self.graph_loss.replay()
+                    g_static.copy_(cap.emb)
+            cap.graph_loss.replay()
             if collectives_active():
                 packed = packed / self.world
                 dist.all_reduce(packed)
@@ -810,23 +821,18 @@ class CloverEngine:
             log_vars = LazyLogVars(names, packed)
             loss = loss.detach().clone()
         else:
-            emb = self._static_emb.detach().requires_grad_()
-            mlm = self._static_mlm.detach().requires_grad_() if self._static_mlm is not None else None
+            emb = cap.emb.detach().requires_grad_()
+            mlm = cap.mlm.detach().requires_grad_() if cap.mlm is not None else None
             losses = self.model.contrastive_losses(emb, mlm)
             loss, log_vars = self._parse_root_scaled(losses)
             loss.backward(gradient=self._root_gradient(loss))
-            self._static_demb.copy_(emb.grad)
+            cap.demb.copy_(emb.grad)
             if mlm is not None:
-                self._static_dmlm.copy_(mlm.grad)
+                cap.dmlm.copy_(mlm.grad)
         self._mark('loss')
         self._replay_backward()
         self._mark('backward')
         return dict(loss=loss.detach(), log_vars=log_vars, num_samples=len(next(iter(batch.values()))))
-
-    # Phase clock of the graphed step (bench.py --phases): events on the main stream at the phase boundaries — the
-    # forward graph, the eager loss section, the backward graphs, reducer.finish() + optimizer.  GPU time between
-    # consecutive marks, averaged by phase_ms(); off (None) unless start_phase_timing() was called.
-    _phase_ev = None
 
     def start_phase_timing(self):
         self._phase_ev = []
@@ -852,9 +858,10 @@ class CloverEngine:
         return lambda q: cl.get(id(q), 'h') in classes
 
     def _replay_backward(self):
-        self.reducer.prepacked = getattr(self, '_prepacked', None) or frozenset()
-        self.graph_bwd.replay()
-        if self.graph_bwd_video is None:
+        cap = self._active
+        self.reducer.prepacked = cap.prepacked
+        cap.graph_bwd.replay()
+        if cap.graph_bwd_video is None:
             return
         # Data-parallel mode: the backward is cut at the encoders' outputs (and once inside the video encoder).  The
         # heads / fusion gradients are complete now: put their buckets on the wire.  Then the text encoder's
@@ -864,16 +871,16 @@ class CloverEngine:
         # (most of the encoder's parameters, little of its time) under the token-heavy early stages;
         # step() -> reducer.finish() sends what is left (early stages + patch embedding: a few MB).
         main = torch.cuda.current_stream()
-        ts = self._bwd_text_stream if self.graph_bwd_text is not None else None
+        ts = self._bwd_text_stream if cap.graph_bwd_text is not None else None
         self.reducer.launch_where(self._ready('h'))
         if ts is not None:
             ts.wait_stream(main)
             with torch.cuda.stream(ts):
-                self.graph_bwd_text.replay()
+                cap.graph_bwd_text.replay()
                 self.reducer.launch_where(self._ready('h', 't'))
-        for i, g in enumerate(self.graph_bwd_video):
+        for i, g in enumerate(cap.graph_bwd_video):
             g.replay()
-            if i + 1 < len(self.graph_bwd_video):          # came down to the in-encoder cut
+            if i + 1 < len(cap.graph_bwd_video):           # came down to the in-encoder cut
                 self.reducer.launch_where(self._ready('h', 'v1') if ts is not None else self._ready('h', 't', 'v1'))
         if ts is not None:
             main.wait_stream(ts)
@@ -885,22 +892,14 @@ class CloverEngine:
         all-gather, InfoNCE/rank losses, logged-scalar all-reduce) stays eager between the two
         replays, so no RCCL call is ever captured and the same code path serves 1..8 GPUs."""
         model = self.model
-        # the recognizer names the batch entries its rank-local part consumes (CloverPretrain: captions + both
-        # masks; CloverFinetune retrieval: captions only) and may return no rank-local loss (mlm is None)
-        aux = {k: None for k in getattr(model, 'CLV_ENCODE_KEYS', ('token_ids', 'input_mask', 'mlm_label',
-                                                                  'v_token_mask'))}
-        self._static_batch = {k: v.clone() for k, v in batch.items()}
-        sb = self._static_batch
-
-        import inspect
+        sb = {k: v.clone() for k, v in batch.items()}
         cut_ok = self.reducer.active and hasattr(model, 'backbone')
-        text_ok = (cut_ok and hasattr(model, 'text_backbone')
-                   and 'text_cut' in inspect.signature(model.encode).parameters)
-        if text_ok and getattr(self, '_bwd_text_stream', None) is None:
+        text_ok = cut_ok and hasattr(model, 'text_backbone') and self._encode_takes_text_cut
+        if text_ok and self._bwd_text_stream is None:
             self._bwd_text_stream = torch.cuda.Stream()
 
-        def encode(vcuts=None, tcuts=None):
-            kw = {k: sb[k] for k in aux}
+        def encode(vcuts=None, tcuts=None):      # (the recognizer may return no rank-local loss: mlm is None)
+            kw = {k: sb[k] for k in self._encode_keys}
             if text_ok:
                 kw['text_cut'] = tcuts
             return model.encode(sb['imgs'], video_cut=vcuts, **kw)
@@ -934,12 +933,7 @@ class CloverEngine:
         # no autograd graph may survive into the capture: a live one pins the parameters'
         # AccumulateGrad nodes to the warm-up stream and their accumulation escapes the hipGraph
         del emb, mlm, vcuts, tcuts
-        for seg in self.segments:
-            seg.flat_g.zero_()
-        self.sumsq.zero_()                    # (the warm-up backwards left norm partial sums: fused-norm mode)
-        if self._norm_tables is not None:
-            self._norm_state.dirty = False
-        self._ft.done.clear()                 # the captured backward holds the first-touch stores of a fresh step
+        self._clear_all()                     # the captured backward holds the first-touch stores of a fresh step
         torch.cuda.synchronize()
         gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         gb2 = None
@@ -949,14 +943,14 @@ class CloverEngine:
         tcuts = [] if text_ok else None
         with torch.cuda.graph(gf, capture_error_mode='thread_local'):
             emb, mlm = encode(vcuts, tcuts)
-        self._static_demb = torch.zeros_like(emb)
-        self._static_dmlm = torch.zeros_like(mlm) if mlm is not None else None
+        demb = torch.zeros_like(emb)
+        dmlm = torch.zeros_like(mlm) if mlm is not None else None
         # Data-parallel jobs: the bf16 wire copy of every bucket is written INSIDE the backward graph that completes its
         # gradients (the pack kernels are plain launches; only the RCCL calls stay between the replays)
         pack = cut_ok
         prepacked = set()
         with torch.cuda.graph(gb, pool=gf.pool(), capture_error_mode='thread_local'):
-            self._backward(lambda: torch.autograd.backward(*roots(emb, mlm, self._static_demb, self._static_dmlm)))
+            self._backward(lambda: torch.autograd.backward(*roots(emb, mlm, demb, dmlm)))
             if pack:
                 prepacked |= self.reducer.pack_where(self._ready('h'))
         if cut_ok:
@@ -980,37 +974,31 @@ class CloverEngine:
                 bwd_cut(tcuts)
                 if pack:
                     prepacked |= self.reducer.pack_where(self._ready('t'), skip=prepacked)
-        self._prepacked = frozenset(prepacked)
-        self._stale_views = self._stale_sinks()    # first-touch slots this geometry's backward never writes
-        for seg in self.segments:
-            seg.flat_g.zero_()                     # a capture pass does not execute kernels; be explicit
-        self.sumsq.zero_()
-        if self._norm_tables is not None and self._norm_state.dirty:
+        cap = _Capture(gf, gb, gb2, gb3, batch=sb, emb=emb, mlm=mlm, demb=demb, dmlm=dmlm, cuts=(vcuts, tcuts),
+                       stale_views=self._stale_sinks(), prepacked=frozenset(prepacked))
+        twice = self._norm_state.dirty
+        self._clear_all()                          # a capture pass does not execute kernels; be explicit
+        if twice:
             raise RuntimeError('fused gradient norm: the captured backward gives a first-touch sink two gradients; build the '
                                'engine with CLOVER_FUSED_NORM=0')
-        self._ft.done.clear()
-        self.graph, self.graph_bwd, self.graph_bwd_video, self.graph_bwd_text = gf, gb, gb2, gb3
-        self._static_emb, self._static_mlm = emb, mlm
-        self.graph_loss, self._loss_io = self._capture_loss_graph()
-        self._static_cuts = (vcuts, tcuts)
-        self._active_sig = self._signature(batch)
-        self._captures[self._active_sig] = tuple(getattr(self, f) for f in self._CAPTURE_FIELDS)
+        cap.graph_loss, cap.loss_io = self._capture_loss_graph(cap)
+        # published whole and last: a capture that raised has left the engine's geometries as they were
+        sig = self._signature(batch)
+        self._captures[sig] = cap
+        self._activate(sig)
         return True
 
-    def _capture_loss_graph(self):
+    def _capture_loss_graph(self, cap):
         """The section between the two encode graphs — contrastive / rank losses on the gathered embeddings, the loss
         sum and its backward down to d emb / d mlm — as a hipGraph over a static gathered tensor.  The all-gather that
         fills it and the all-reduce of the logged scalars stay eager (no RCCL call is ever captured); the gather's
         backward is the local slice (gather_loss.py:64-72), taken inside the graph.  CLOVER_LOSS_GRAPH=1 is ignored with
         virtual_ranks > 1: that loss section runs once per k replays, on a tensor k times the captured one."""
-        import inspect
         model = self.model
-        if (os.environ.get('CLOVER_LOSS_GRAPH', '0') != '1' or self.virtual_ranks > 1
-                or not hasattr(model, 'contrastive_losses')
-                or 'gathered' not in inspect.signature(model.contrastive_losses).parameters
+        if (os.environ.get('CLOVER_LOSS_GRAPH', '0') != '1' or self.virtual_ranks > 1 or not self._loss_takes_gathered
                 or not getattr(getattr(model, 'ssl_loss', None), 'equal_batch', False)):
             return None, None
-        emb = self._static_emb
+        emb = cap.emb
         B = emb.shape[0]
         g_static = torch.zeros((self.world * B,) + tuple(emb.shape[1:]), device=emb.device, dtype=torch.float32)
         g_static[self.rank * B:(self.rank + 1) * B].copy_(emb)
@@ -1018,13 +1006,13 @@ class CloverEngine:
 
         def run():
             g = g_static.detach().requires_grad_()
-            mlm = self._static_mlm.detach().requires_grad_() if self._static_mlm is not None else None
+            mlm = cap.mlm.detach().requires_grad_() if cap.mlm is not None else None
             losses = model.contrastive_losses(None, mlm, gathered=g)
             loss, names, packed = self._parse_root_scaled(losses, reduce=False)
             loss.backward(gradient=self._root_gradient(loss))
-            self._static_demb.copy_(g.grad[self.rank * B:(self.rank + 1) * B])
+            cap.demb.copy_(g.grad[self.rank * B:(self.rank + 1) * B])
             if mlm is not None:
-                self._static_dmlm.copy_(mlm.grad)
+                cap.dmlm.copy_(mlm.grad)
             out.update(names=names, packed=packed, loss=loss.detach())
 
         side = torch.cuda.Stream()

@@ -77,7 +77,7 @@ class BucketedGradReducer:
         self.seen = {}
         self._producers = [[] for _ in self.buckets]
 
-    prepacked = frozenset()      # buckets whose bf16 wire copy the replayed backward graphs have already written (engine)
+    prepacked = frozenset()      # buckets whose bf16 wire copy the replayed backward graphs have already written (the engine's active capture: ``prepacked``)
 
     def pack_where(self, ready, skip=()):
         """Pack (fp32 slab slice -> bf16 wire slab, no collective) every bucket all of whose parameters satisfy `ready` —

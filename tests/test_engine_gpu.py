@@ -330,7 +330,7 @@ def test_graph_capture_equals_eager_and_loss_decreases(loss_graph, monkeypatch):
         if mode == 'graph':
             eng.step(b)
             assert eng.capture(b)
-            assert (eng.graph_loss is not None) == (loss_graph == '1')
+            assert (eng._active.graph_loss is not None) == (loss_graph == '1')
             assert eng.input_buffers() is not None
             b_run = eng.input_buffers()                      # a loader writing straight into the static buffers
         else:
@@ -525,14 +525,14 @@ def test_finetune_engine_graph_equals_eager_and_trains(monkeypatch):
 
     eager, _ = run('eager')
     graph, eng = run('graph')
-    assert eng.graph_bwd_video is None
+    assert eng._active.graph_bwd_video is None
     monkeypatch.setenv('CLOVER_FORCE_COLLECTIVES', '1')
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ.setdefault('MASTER_PORT', '29563')
     dist.init_process_group('nccl', rank=0, world_size=1, device_id=torch.device('cuda', 0))
     try:
         rccl, eng = run('rccl')
-        assert eng.reducer.active and eng.graph_bwd_video is not None and eng.graph_bwd_text is not None
+        assert eng.reducer.active and eng._active.graph_bwd_video is not None and eng._active.graph_bwd_text is not None
     finally:
         dist.destroy_process_group()
     print(eager, graph, rccl)
@@ -582,7 +582,7 @@ def test_rccl_code_path_on_one_gpu(monkeypatch):
     try:
         got, eng = run()
         assert eng.reducer.active and len(eng.reducer.buckets) > 1
-        assert len(eng.graph_bwd_video) == 2 and eng.graph_bwd_text is not None        # four backward graphs
+        assert len(eng._active.graph_bwd_video) == 2 and eng._active.graph_bwd_text is not None        # four backward graphs
         classes = {eng._pclass.get(id(q), 'h') for ps in eng.reducer._bucket_params for q in ps}
         assert classes == {'h', 't', 'v1', 'v0'}
         assert all(len({eng._pclass.get(id(q), 'h') for q in ps}) == 1 for ps in eng.reducer._bucket_params)
@@ -599,7 +599,7 @@ def test_rccl_code_path_on_one_gpu(monkeypatch):
         assert total == 2 * sum(seg.flat_g.numel() for seg in eng.segments) and left <= 0.05 * total, (left, total)
         # every bucket's bf16 wire copy is written inside the backward graph that completes it (no eager pack launches),
         # and the stall of the compute stream on the comm stream is recorded
-        assert eng._prepacked == frozenset(range(len(eng.reducer.buckets))), eng._prepacked
+        assert eng._active.prepacked == frozenset(range(len(eng.reducer.buckets))), eng._active.prepacked
         eng.reducer.start_timing()
         eng.step(b)
         torch.cuda.synchronize()
@@ -916,6 +916,47 @@ def test_first_touch_slots_across_a_geometry_switch(mode, monkeypatch):
             dist.destroy_process_group()
     for n in final['0']:
         assert torch.allclose(final['0'][n], final['1'][n], rtol=0, atol=1e-6), n
+
+
+def test_failed_capture_leaves_the_engine_as_it_was(monkeypatch):
+    """A capture() that raises part-way publishes nothing: the captured geometry stays active with its own graphs and
+    buffers and goes on training exactly as an engine that never saw the failure; once the cause is gone the other
+    geometry captures.  The failure is a host exception raised where the loss-graph stage would run, after every
+    backward graph has been captured."""
+    from clover_amd.engine import CloverEngine
+    torch.manual_seed(3)
+    wide = dict(imgs=torch.randn(128, 128, device=DEV))
+    narrow = dict(imgs=torch.randn(64, 128, device=DEV))
+
+    def engine():
+        m = _TwoPathToy().to(DEV)
+        eng = CloverEngine(m, wide, lr=1e-2, weight_decay=0.0, grad_clip=0.0, max_iters=10 ** 9)
+        eng.dry_step(wide)
+        assert eng.capture(wide)
+        return m, eng
+
+    m_ref, ref = engine()
+    for _ in range(5):
+        ref.step(wide)
+    m, eng = engine()
+    for _ in range(2):
+        eng.step(wide)
+    graph, active, sig = eng.graph, eng._active, eng._active_sig
+
+    def boom(cap):
+        raise RuntimeError('loss graph stage failed')
+    with monkeypatch.context() as mp:
+        mp.setattr(eng, '_capture_loss_graph', boom)
+        with pytest.raises(RuntimeError, match='loss graph stage failed'):
+            eng.step(narrow)
+    assert len(eng._captures) == 1
+    assert eng.graph is graph and eng._active is active and eng._captures[sig] is active and eng._active_sig == sig
+    for _ in range(3):
+        assert bool(torch.isfinite(eng.step(wide)['loss']))
+    for (n, p), (_, q) in zip(m.named_parameters(), m_ref.named_parameters()):
+        assert torch.allclose(p, q, rtol=0, atol=1e-6), n
+    eng.step(narrow)
+    assert len(eng._captures) == 2 and eng._active is not active
 
 
 @pytest.mark.usefixtures('strict_own_gemm')

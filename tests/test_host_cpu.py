@@ -784,6 +784,31 @@ def test_sumsq_range_table_host_logic():
     assert n0 == 0
 
 
+@pytest.mark.parametrize('spans,total,want', [
+    ([], 10, [(0, 10)]),                                             # no span: everything is left over
+    ([], 0, []),
+    ([(0, 3), (7, 10)], 10, [(3, 7)]),                               # spans touching both ends
+    ([(2, 4), (4, 6), (9, 12)], 16, [(0, 2), (6, 9), (12, 16)]),     # adjacent spans leave no empty range between them
+    ([(1, 8), (3, 5), (6, 11), (11, 11)], 14, [(0, 1), (11, 14)]),   # overlapping, nested and empty spans
+    ([(0, 10)], 10, []),                                             # one span covering everything
+])
+def test_complement_of_spans_tiles_the_slab(spans, total, want):
+    """engine._complement (the zero views of the first-touch scheme, the range tables of the fused norm): the ranges and
+    the spans together cover every element of [0, total), no element lies in a range and a span or in two ranges, the
+    ranges are in order and none is empty."""
+    from clover_amd.engine import _complement
+    ranges = _complement(spans, total)
+    assert ranges == want
+    assert all(0 <= a < b <= total for a, b in ranges)
+    assert all(b0 < a1 for (_, b0), (a1, _) in zip(ranges, ranges[1:]))      # ordered, and not merely split in two
+    in_span, in_range = np.zeros(total, dtype=np.int64), np.zeros(total, dtype=np.int64)
+    for a, b in spans:
+        in_span[a:b] = 1
+    for a, b in ranges:
+        in_range[a:b] += 1
+    assert np.array_equal(in_span + in_range, np.ones(total, dtype=np.int64))
+
+
 def test_bench_dump_outputs_fixed_sample(tmp_path):
     """bench.py --dump-outputs: the losses and the gradient norm as float64 scalars, the parameters and AdamW moments as
     float32 samples at indices fixed by the parameter names — the same arrays for two slab layouts of the same weights,

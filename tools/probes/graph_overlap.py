@@ -82,9 +82,10 @@ class Stamped:
 
 
 eng.graph = Stamped(eng.graph, 'forward')
-eng.graph_bwd = Stamped(eng.graph_bwd, 'backward')
-if getattr(eng, 'graph_loss', None) is not None:
-    eng.graph_loss = Stamped(eng.graph_loss, 'loss')
+cap = eng._active
+cap.graph_bwd = Stamped(cap.graph_bwd, 'backward')
+if cap.graph_loss is not None:
+    cap.graph_loss = Stamped(cap.graph_loss, 'loss')
 for _ in range(10):
     eng.step(batch)
 torch.cuda.synchronize()

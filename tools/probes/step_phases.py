@@ -31,11 +31,12 @@ for _ in range(N):
     e[0].record()
     eng.graph.replay()
     e[1].record()
-    emb = eng._static_emb.detach().requires_grad_(); mlm = eng._static_mlm.detach().requires_grad_()
+    cap = eng._active
+    emb = cap.emb.detach().requires_grad_(); mlm = cap.mlm.detach().requires_grad_()
     losses = model.contrastive_losses(emb, mlm)
     loss, lv = model._parse_losses(losses)
     loss.backward()
-    eng._static_demb.copy_(emb.grad); eng._static_dmlm.copy_(mlm.grad)
+    cap.demb.copy_(emb.grad); cap.dmlm.copy_(mlm.grad)
     e[2].record()
     eng._replay_backward()
     e[3].record()
