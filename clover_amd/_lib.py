@@ -86,6 +86,12 @@ class ClvLnReduceEntry(C.Structure):
 LN_REDUCE_MAX = 64
 
 
+class ClvGemmPlan(C.Structure):
+    """Mirror of ``struct ClvGemmPlan`` (include/clover_hip.h): what clv_gemm_nt_ex launches for a shape."""
+    _fields_ = [(n, _i32) for n in ('kernel', 'BM', 'BN', 'waves', 'ring', 'splitk', 'rot', 'pc', 'grid', 'units_max_xcd',
+                                    'slots_xcd', 'bias_in_lds')]
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),
@@ -158,6 +164,7 @@ SIGNATURES = {
     'clv_gemm_nt': (C.c_int, [_p] * 6 + [_i64, _i32, _i32, _i64, _i64, _i64, _i32, _p]),
     'clv_gemm_nt_work_bytes': (C.c_int64, [_i64, _i32, _i32]),
     'clv_gemm_nt_ex': (C.c_int, [_p] * 6 + [_i64, _i32, _i32, _i64, _i64, _i64, _i32, _p, _i64, _p]),
+    'clv_gemm_nt_plan': (C.c_int, [_i64, _i32, _i32, _i32, C.POINTER(ClvGemmPlan)]),
     'clv_transpose_batch': (C.c_int, [_p, _p, _p, _i32, _i32, _p]),
     'clv_layernorm_bwd_needs_reduce': (C.c_int, [_i64, _i32]),
     'clv_ln_reduce_batch': (C.c_int, [_p, _i32, _p]),

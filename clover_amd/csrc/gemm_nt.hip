@@ -1152,6 +1152,46 @@ GnPlan gn_plan(int64_t M, int N, int K, bool allow_split) {
     return p;
 }
 
+// The plan of a call as clv_gemm_nt_ex makes it: slices only with a work buffer that holds them.
+GnPlan gn_plan_for(int64_t M, int N, int K, bool with_work, int64_t work_bytes) {
+    GnPlan pl = gn_plan(M, N, K, with_work);
+    if (pl.splitk > 1 && work_bytes < (int64_t)pl.splitk * M * N * 4) pl = gn_plan(M, N, K, false);
+    return pl;
+}
+
+// What a plan launches: kernel, ring, XCD column split, grid.  gn_run dispatches on this record and clv_gemm_nt_plan hands it
+// out, so what the tests claim about a shape is what runs.
+ClvGemmPlan gn_geom(const GnPlan& pl, int64_t M, int N, int K) {
+    ClvGemmPlan g;
+    g.kernel = pl.ws;
+    g.BM = pl.BM;
+    g.BN = pl.BN;
+    g.splitk = pl.splitk;
+    const int tilesN = (N + pl.BN - 1) / pl.BN;
+    const int nmblk = (int)((M + pl.BM - 1) / pl.BM);
+    g.pc = gn_pick_pc((int64_t)M * K * 2, (int64_t)N * K * 2, tilesN);
+    g.units_max_xcd = ((nmblk + 8 / g.pc - 1) / (8 / g.pc)) * ((tilesN + g.pc - 1) / g.pc) * pl.splitk;
+    if (pl.ws) {                                              // consumers + 2 producers, one workgroup per CU, ring of 4
+        g.waves = (pl.ws == 1 ? 8 : 4) + 2;
+        g.ring = 4;
+        g.rot = 0;                                            // the wave-specialised kernels walk K in order
+        g.slots_xcd = 32;
+    } else {
+        // persistent workgroups: per_cu per CU, 32 * per_cu slots per XCD, never more than the fullest XCD's units
+        const int BM = pl.BM, BN = pl.BN, W = pl.W;
+        const int per_cu = (BM == 64 && (BN == 128 || BN == 192)) ? 2 : (BM == 64 && BN == 64) ? 3 : (BM == 128 && W == 8 && pl.r2) ? 2 : 1;
+        g.waves = W;
+        g.ring = (BM == 128 && BN == 128 && W == 8) ? (pl.r2 ? 2 : 4) : (BM == 64 && BN == 192) ? 2 : 3;
+        g.rot = pl.rot;
+        g.slots_xcd = 32 * per_cu;
+    }
+    g.grid = 8 * (g.units_max_xcd < g.slots_xcd ? g.units_max_xcd : g.slots_xcd);
+    // the one-pass kernels keep the bias row in LDS up to GN_MAX_BIAS columns; wider outputs and the reduce kernel of a
+    // sliced launch read it from global memory (rounded to 16 bits either way)
+    g.bias_in_lds = pl.splitk == 1 && N <= GN_MAX_BIAS;
+    return g;
+}
+
 int gn_run(const void* a, const void* b, const float* bias, const void* aux, void* c, void* c2, int64_t M, int32_t N,
            int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t epilogue, void* work, int64_t work_bytes, void* stream) {
     if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return CLV_ERR_ARG;
@@ -1169,10 +1209,7 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
     // (tools/probes/gemm_tiles.py; with the XCD column split the 450-tile qkv of stage 3 is faster on 128 x 128).
     // 128 x 128 tiles run on EIGHT waves (64 x 32 each) with a ring of 2: two workgroups = 16 waves per CU instead of 8 —
     // 0-5 % on every shape of the class (gemm_tiles.py: fc1 s3 24.8 -> 23.6, fc1 s1 29.5 -> 27.9, dqkv s2 20.2 -> 19.7 us)
-    GnPlan pl = gn_plan(M, N, K, work != nullptr);
-    if (pl.splitk > 1 && work_bytes < (int64_t)pl.splitk * M * N * 4) pl = gn_plan(M, N, K, false);
-    int BM = pl.BM, BN = pl.BN, W = pl.W;
-    bool r2 = pl.r2;
+    GnPlan pl = gn_plan_for(M, N, K, work != nullptr, work_bytes);
     hipStream_t st = (hipStream_t)stream;
 #ifdef GN_LAB
     // Tile lab only (tools/probes/gemm_lab.cpp and the -DGN_LAB variant library of tools/probes/build_wg_variants.sh): a forced
@@ -1199,38 +1236,36 @@ int gn_run(const void* a, const void* b, const float* bias, const void* aux, voi
         return CLV_ERR_UNSUPPORTED;
     }
     if (force) {
-        BM = atoi(force);
+        pl.BM = atoi(force);
         const char* x = strchr(force, 'x');
-        if (x) BN = atoi(x + 1);
+        if (x) pl.BN = atoi(x + 1);
         const char* w = strchr(force, 'w');
-        W = w ? atoi(w + 1) : (BM == 256 ? 8 : 4);
-        r2 = strstr(force, "r2") != nullptr;
+        pl.W = w ? atoi(w + 1) : (pl.BM == 256 ? 8 : 4);
+        pl.r2 = strstr(force, "r2") != nullptr;
         pl.ws = 0;                                            // a forced tile runs on gemm_nt_kernel
     }
 #endif
+    // class, ring, pc and grid come from gn_geom, the function clv_gemm_nt_plan reports from: the entry cannot drift from
+    // the launch
+    const ClvGemmPlan g = gn_geom(pl, M, N, K);
+    const int BM = g.BM, BN = g.BN, W = pl.W;
     const int tilesN = (N + BN - 1) / BN;
     const int nmblk = (int)((M + BM - 1) / BM);
-    if (pl.ws) {                                              // wave-specialised classes: one workgroup per CU
-        const int pcw = gn_pick_pc((int64_t)M * K * 2, (int64_t)N * K * 2, tilesN);
-        const int max_units = ((nmblk + 8 / pcw - 1) / (8 / pcw)) * ((tilesN + pcw - 1) / pcw) * pl.splitk;
-        const unsigned gridw = (unsigned)(8 * (max_units < 32 ? max_units : 32));
-#define GN_WARGS epilogue, st, gridw, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, \
-                 K, lda, ldb, ldc, tilesN, nmblk, pcw, pl.splitk, (float*)work
-        if (pl.ws == 1) return gn_launch_ws<128, 128, 2, 4, 2, 4>(GN_WARGS);
-        return gn_launch_ws<64, 128, 2, 2, 2, 4>(GN_WARGS);
+    const unsigned grid = (unsigned)g.grid;
+    if (g.kernel) {                                           // wave-specialised classes: one workgroup per CU
+#define GN_WARGS epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, \
+                 K, lda, ldb, ldc, tilesN, nmblk, g.pc, g.splitk, (float*)work
+        if (g.kernel == 1 && g.ring == 4) return gn_launch_ws<128, 128, 2, 4, 2, 4>(GN_WARGS);
+        if (g.kernel == 2 && g.ring == 4) return gn_launch_ws<64, 128, 2, 2, 2, 4>(GN_WARGS);
 #undef GN_WARGS
+        return CLV_ERR_UNSUPPORTED;
     }
-    // persistent workgroups: per_cu per CU, 32 * per_cu slots per XCD, never more than the fullest XCD's units
-    const int per_cu = (BM == 64 && (BN == 128 || BN == 192)) ? 2 : (BM == 64 && BN == 64) ? 3 : (BM == 128 && W == 8 && r2) ? 2 : 1;
-    const int pc = gn_pick_pc((int64_t)M * K * 2, (int64_t)N * K * 2, tilesN);
-    const int max_units_xcd = ((nmblk + 8 / pc - 1) / (8 / pc)) * ((tilesN + pc - 1) / pc) * pl.splitk;
-    const unsigned grid = (unsigned)(8 * (max_units_xcd < 32 * per_cu ? max_units_xcd : 32 * per_cu));
 #define GN_ARGS epilogue, st, grid, (const bf16_t*)a, (const bf16_t*)b, bias, (const bf16_t*)aux, (bf16_t*)c, (bf16_t*)c2, M, N, K, \
-                lda, ldb, ldc, tilesN, nmblk, pc, pl.splitk, pl.rot, (float*)work
-    if (BM == 128 && BN == 128 && W == 8 && r2) return gn_launch<128, 128, 2, 4, 2>(GN_ARGS);   // 32 KiB stages x 2, two WGs per CU
-    if (BM == 64 && BN == 128 && W == 4) return gn_launch<64, 128, 2, 2, 3>(GN_ARGS);     // 24 KiB stages x 3, two WGs per CU
-    if (BM == 128 && BN == 192 && W == 8) return gn_launch<128, 192, 4, 2, 3>(GN_ARGS);   // 40 KiB stages x 3, eight waves of 32 x 96
-    if (BM == 64 && BN == 192 && W == 4) return gn_launch<64, 192, 2, 2, 2>(GN_ARGS);     // 32 KiB stages x 2, four waves of 32 x 96, two WGs per CU
+                lda, ldb, ldc, tilesN, nmblk, g.pc, g.splitk, g.rot, (float*)work
+    if (BM == 128 && BN == 128 && W == 8 && g.ring == 2) return gn_launch<128, 128, 2, 4, 2>(GN_ARGS);   // 32 KiB stages x 2, two WGs per CU
+    if (BM == 64 && BN == 128 && W == 4 && g.ring == 3) return gn_launch<64, 128, 2, 2, 3>(GN_ARGS);     // 24 KiB stages x 3, two WGs per CU
+    if (BM == 128 && BN == 192 && W == 8 && g.ring == 3) return gn_launch<128, 192, 4, 2, 3>(GN_ARGS);   // 40 KiB stages x 3, eight waves of 32 x 96
+    if (BM == 64 && BN == 192 && W == 4 && g.ring == 2) return gn_launch<64, 192, 2, 2, 2>(GN_ARGS);     // 32 KiB stages x 2, four waves of 32 x 96, two WGs per CU
 #ifdef GN_LAB
     if (BM == 256 && BN == 128 && W == 8) return gn_launch<256, 128, 4, 2, 3>(GN_ARGS);   // 48 KiB stages x 3
     if (BM == 128 && BN == 128 && W == 8) return gn_launch<128, 128, 2, 4, 4>(GN_ARGS);   // 32 KiB stages x 4
@@ -1252,6 +1287,14 @@ extern "C" int64_t clv_gemm_nt_work_bytes(int64_t M, int32_t N, int32_t K) {
     if (M <= 0 || N <= 0 || K <= 0 || !clv_gemm_nt_supported(M, N, K)) return 0;
     const GnPlan pl = gn_plan(M, N, K, true);
     return pl.splitk > 1 ? (int64_t)pl.splitk * M * N * 4 : 0;
+}
+
+extern "C" int clv_gemm_nt_plan(int64_t M, int32_t N, int32_t K, int32_t with_work, ClvGemmPlan* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0) return CLV_ERR_ARG;
+    if (!clv_gemm_nt_supported(M, N, K)) return CLV_ERR_UNSUPPORTED;
+    // with_work: a work buffer of clv_gemm_nt_work_bytes or more (which covers every slice count the planner can pick)
+    *out = gn_geom(gn_plan_for(M, N, K, with_work != 0, INT64_MAX), M, N, K);
+    return CLV_OK;
 }
 
 extern "C" int clv_gemm_nt_ex(const void* a, const void* b, const float* bias, const void* aux, void* c, void* c2, int64_t M,

@@ -1247,7 +1247,10 @@ def gemm_nt(a, b, bias=None, aux=None, epilogue=GEMM_EPI_NONE, out=None):
     N = b.shape[0]
     assert a.dtype == BF16 and b.dtype == BF16 and a.stride(1) == 1 and b.stride(1) == 1 and b.shape[1] == K
     c = out if out is not None else torch.empty(M, N, device=a.device, dtype=BF16)
-    c2 = torch.empty_like(c) if epilogue in (GEMM_EPI_BIAS_GELU, GEMM_EPI_BIAS_GELU_D) else None
+    # c2 is addressed with c's row stride: for an `out` that is a column slice, empty_like would hand back a dense [M, N]
+    # and the kernel would write past its end
+    c2 = (torch.empty_strided(c.shape, c.stride(), device=c.device, dtype=BF16)
+          if epilogue in (GEMM_EPI_BIAS_GELU, GEMM_EPI_BIAS_GELU_D) else None)
     if bias is not None and bias.dtype != torch.float32:
         bias = bias.float()
     if aux is not None:

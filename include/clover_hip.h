@@ -505,7 +505,11 @@ int clv_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, c
  *   CLV_GEMM_EPI_BIAS_GELU_D  c2 = GELU_erf'(acc + bias) (what the backward needs of the pre-activation, computed where its
  *                             erf / exp are in hand anyway), c = GELU_erf(acc + bias)
  *   CLV_GEMM_EPI_MUL        c = acc * aux                 (aux = that c2: the GELU backward without a transcendental)
- * Needs N % 8 == 0, K % 64 == 0, 16-byte aligned pointers (clv_gemm_nt_supported); fp32 accumulation. */
+ * Needs N % 8 == 0, K % 64 == 0, 16-byte aligned pointers (clv_gemm_nt_supported); fp32 accumulation.
+ * The bias is ROUNDED TO THE 16-BIT TYPE before it is added (on every path: the row kept in LDS, the read from global
+ * memory for N > 3072, the reduce kernel of a sliced launch) — part of the result, pinned by tests/test_gemm_nt_gpu.py.
+ * aux and c2 are addressed with ldc, like c: element (m, n) of each lies at m * ldc + n.  Columns [N, ldc) of c / c2 are
+ * never written. */
 #define CLV_GEMM_EPI_NONE 0
 #define CLV_GEMM_EPI_BIAS 1
 #define CLV_GEMM_EPI_BIAS_GELU 2
@@ -525,6 +529,26 @@ int64_t clv_gemm_nt_work_bytes(int64_t M, int32_t N, int32_t K);
 int clv_gemm_nt_ex(const void* a, const void* b, const float* bias, const void* aux, void* c, void* c2, int64_t M,
                    int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t epilogue, void* work,
                    int64_t work_bytes, void* stream);
+/* What clv_gemm_nt_ex launches for a shape under the current CLV_GEMM_SPLITK / CLV_GEMM_ROT (host only, no GPU needed;
+ * added to ABI 18 — a new symbol, nothing existing changes).  with_work: 0 = as with work == NULL (never sliced), 1 = as
+ * with a work buffer large enough for the plan.  The launch dispatches on the same record, so the entry cannot drift from
+ * it.  Returns CLV_ERR_ARG / CLV_ERR_UNSUPPORTED like the GEMM itself.
+ *   kernel         0 gemm_nt_kernel (every wave stages and multiplies), 1 gemm_ws_kernel 128 x 128, 2 gemm_ws_kernel 64 x 128
+ *                  (wave-specialised: producer waves stage, consumer waves multiply)
+ *   BM, BN         output tile;  waves: per workgroup (the wave-specialised classes: consumers + 2 producers = 10 / 6)
+ *   ring           stages of the LDS ring
+ *   splitk         K slices (> 1: fp32 slabs in `work` + the reduce kernel, which applies the epilogue)
+ *   rot            1: the K walk of each unit starts at a rotated stage (CLV_GEMM_ROT=1, K >= 192, kernel 0 only)
+ *   pc             column partitions of the XCD split: XCD x owns row blocks = x / pc (mod 8 / pc), column tiles = x % pc (mod pc)
+ *   grid           workgroups = 8 * min(units_max_xcd, slots_xcd)
+ *   units_max_xcd  (tile, slice) units of the fullest XCD;  slots_xcd: persistent workgroups per XCD — more units than
+ *                  slots means some workgroup walks several units
+ *   bias_in_lds    1: the bias row is staged in LDS as 16-bit values; 0: read from global memory (N > 3072, or splitk > 1:
+ *                  by the reduce kernel) and rounded to 16 bits there */
+typedef struct ClvGemmPlan {
+    int32_t kernel, BM, BN, waves, ring, splitk, rot, pc, grid, units_max_xcd, slots_xcd, bias_in_lds;
+} ClvGemmPlan;
+int clv_gemm_nt_plan(int64_t M, int32_t N, int32_t K, int32_t with_work, ClvGemmPlan* out);
 /* Batched transposes of bf16 matrices in one launch (the engine's W^T shadows, refreshed after every optimizer step).
  * table: n_entries x {int64 src_off, dst_off (elements from src_base / dst_base); int32 rows, cols, tile_begin,
  * tiles_c} on the device; entry e covers ceil(rows/64) * tiles_c tiles starting at tile_begin (tiles_c =
