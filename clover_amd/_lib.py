@@ -35,7 +35,7 @@ def half_dtype():
     import torch
     return torch.float16 if HALF_F16 else torch.bfloat16
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 ERRORS = {-1: 'CLV_ERR_ARG (bad argument)', -2: 'CLV_ERR_UNSUPPORTED (shape not supported by the kernels)',
           -3: 'CLV_ERR_LAUNCH (HIP launch failed)'}
@@ -92,6 +92,16 @@ class ClvGemmPlan(C.Structure):
                                     'slots_xcd', 'bias_in_lds')]
 
 
+class ClvRowgemmPlan(C.Structure):
+    """Mirror of ``struct ClvRowgemmPlan`` (include/clover_hip.h): what clv_rowgemm launches for a shape."""
+    _fields_ = [(n, _i32) for n in ('TN', 'waves', 'ny', 'gx', 'lds_bytes', 'trips')]
+
+
+class ClvMlpFusedPlan(C.Structure):
+    """Mirror of ``struct ClvMlpFusedPlan`` (include/clover_hip.h): how clv_mlp_fused_fwd / _bwd cut the rows."""
+    _fields_ = [(n, _i32) for n in ('grid', 'tiles_min', 'tiles_max', 'trips', 'half_group')]
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),
@@ -135,7 +145,9 @@ SIGNATURES = {
     'clv_rowgemm_supported': (C.c_int, [_i32, _i32, _i32]),
     'clv_rowgemm': (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p]),
     'clv_rowgemm_xs': (C.c_int, [_p] * 11 + [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _f, _p, _i32, _p]),
+    'clv_rowgemm_plan': (C.c_int, [_i64, _i32, _i32, _i32, _i32, C.POINTER(ClvRowgemmPlan)]),
     'clv_mlp_fused_supported': (C.c_int, [_i32, _i32]),
+    'clv_mlp_fused_plan': (C.c_int, [_i64, C.POINTER(ClvMlpFusedPlan)]),
     'clv_mlp_fused_fwd': (C.c_int, [_p] * 10 + [_i64, _i32, _i32, _f, _p, _i32, _p]),
     'clv_mlp_fused_bwd': (C.c_int, [_p] * 13 + [_i64, _i32, _i32, _p, _i32, _p]),
     'clv_colsum': (C.c_int, [_p, _p, _i64, _i32, _i32, _p]),

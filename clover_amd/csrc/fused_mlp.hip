@@ -56,10 +56,19 @@ __device__ __forceinline__ uint2 fm_tr4(const bf16_t* base, int LD, int row0, in
 struct FmRange {
     int64_t row0, row1;     // this workgroup's token rows
 };
+// 16-token tiles [t0, t1) of workgroup b of `grid`: the kernels' row ranges and what clv_mlp_fused_plan reports
+struct FmTiles {
+    int64_t t0, t1;
+};
+__host__ __device__ __forceinline__ FmTiles fm_tile_bounds(int64_t M, unsigned grid, unsigned b) {
+    const int64_t tiles = (M + 15) / 16, nb = grid;
+    const int64_t t0 = tiles * b / nb, t1 = tiles * (b + 1) / nb;
+    return FmTiles{t0, t1};
+}
 __device__ __forceinline__ FmRange fm_range(int64_t M) {
     // contiguous, 16-aligned row ranges, one per workgroup
-    const int64_t tiles = (M + 15) / 16, nb = gridDim.x;
-    const int64_t t0 = tiles * blockIdx.x / nb, t1 = tiles * (blockIdx.x + 1) / nb;
+    const FmTiles tb = fm_tile_bounds(M, gridDim.x, blockIdx.x);
+    const int64_t t0 = tb.t0, t1 = tb.t1;
     FmRange r;
     r.row0 = t0 * 16;
     r.row1 = t1 * 16 < M ? t1 * 16 : M;
@@ -522,6 +531,26 @@ int fm_grid(int64_t M) {
 }  // namespace
 
 extern "C" int clv_mlp_fused_supported(int32_t C, int32_t hidden) { return C == FM_C && hidden == FM_H; }
+
+extern "C" int clv_mlp_fused_plan(int64_t M, ClvMlpFusedPlan* out) {
+    if (!out || M <= 0) return CLV_ERR_ARG;
+    const int grid = fm_grid(M);
+    int64_t lo = INT64_MAX, hi = 0;
+    int odd = 0;
+    for (int b = 0; b < grid; ++b) {
+        const FmTiles tb = fm_tile_bounds(M, (unsigned)grid, (unsigned)b);
+        const int64_t n = tb.t1 - tb.t0;
+        lo = n < lo ? n : lo;
+        hi = n > hi ? n : hi;
+        odd |= (int)(n & 1);
+    }
+    out->grid = grid;
+    out->tiles_min = (int32_t)lo;
+    out->tiles_max = (int32_t)hi;
+    out->trips = (int32_t)(((hi + 1) / 2 + FM_NW - 1) / FM_NW);      // groups of two tiles per wave, fullest workgroup
+    out->half_group = odd;
+    return CLV_OK;
+}
 
 extern "C" int clv_mlp_fused_fwd(const void* a, const void* res, void* sum_out, float* mean, float* rstd, const void* w1f,
                                  const float* b1f, const void* w2, const float* b2, void* out, int64_t M, int32_t C,

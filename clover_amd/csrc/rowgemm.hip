@@ -208,44 +208,41 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 && KS <= 4) ? 6 : 1) rowgemm
     }
 }
 
-template <int KS, bool STD, int EPI, int NW = RG_WAVES>
-int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float* rstd, void* xhat_out, const void* wt,
-              const float* bias, const void* pre_in, void* y, void* pre_out, int64_t M, int N, int ldx, int ldy,
-              float eps, hipStream_t st, const float* xscale = nullptr, int rps = 1) {
-    using C = RGCfg<KS>;
-    constexpr int NST = (EPI == EPI_NONE) ? 1 : 2;
-    const size_t lds = (size_t)C::TN * C::LDW * 2 + (size_t)NW * NST * 16 * C::LDO * 2 + (size_t)C::TN * 4;
-    if (lds > 160 * 1024) return CLV_ERR_UNSUPPORTED;
+// ---- "decide": what a launch looks like, as plain functions of (K / 32, prologue, epilogue, M, N).  launch_rg below and the
+// host entry clv_rowgemm_plan both go through rg_decide, so what the entry reports is what is launched.
+constexpr size_t rg_lds_bytes(int KS, int EPI, int NW) {
+    const size_t TN = (KS <= 12 && KS > 4) ? 128 : 64, LDW = (size_t)KS * 32 + 8, LDO = TN + 8, NST = (EPI == EPI_NONE) ? 1 : 2;
+    return TN * LDW * 2 + (size_t)NW * NST * 16 * LDO * 2 + TN * 4;
+}
+// waves per workgroup: a function of the instantiation alone (never of M, N), so it is also the kernel's template argument
+constexpr int rg_waves(int KS, bool STD, int EPI) {
+    const size_t TN = (KS <= 12 && KS > 4) ? 128 : 64, LDW = (size_t)KS * 32 + 8, LDO = TN + 8, NST = (EPI == EPI_NONE) ? 1 : 2;
     // a weight tile of >= 64 KB leaves ONE workgroup per CU: eight waves share it instead of four (K = 288 / 384: the
     // stage-0 qkv input gradient and fc2)
-    if constexpr (NW == RG_WAVES && KS >= 6 && KS <= 12) {
-        constexpr int wv = RG_BIG_TILE_WAVES;
-        const size_t wbytes = (size_t)C::TN * C::LDW * 2 + (size_t)C::TN * 4, per_wave = (size_t)NST * 16 * C::LDO * 2;
+    if (KS >= 6 && KS <= 12) {
+        const int wv = RG_BIG_TILE_WAVES;
+        const size_t wbytes = TN * LDW * 2 + TN * 4, per_wave = NST * 16 * LDO * 2;
         if (wbytes >= 48 * 1024) {
-            if ((wv == 12 || (KS <= 8 && wv >= 8)) && wbytes + 12 * per_wave <= 160 * 1024)
-                return launch_rg<KS, STD, EPI, 12>(x, res, sum_out, mean, rstd, xhat_out, wt, bias, pre_in, y, pre_out, M, N, ldx,
-                                                   ldy, eps, st, xscale, rps);
-            if (wv >= 8 && wbytes + 8 * per_wave <= 160 * 1024)
-                return launch_rg<KS, STD, EPI, 8>(x, res, sum_out, mean, rstd, xhat_out, wt, bias, pre_in, y, pre_out, M, N, ldx,
-                                                  ldy, eps, st, xscale, rps);
+            if ((wv == 12 || (KS <= 8 && wv >= 8)) && wbytes + 12 * per_wave <= 160 * 1024) return 12;
+            if (wv >= 8 && wbytes + 8 * per_wave <= 160 * 1024) return 8;
         }
     }
     // K <= 128 with the GELU' epilogue (fc1's input gradient at stage 0) or the LayerNorm prologue (qkv, fc1): 8-wave
     // workgroups put 24 waves on a CU where five 4-wave ones (LDS) put 20 — 108 -> 91 us for the former.  The prologue
     // variants fit the 80 VGPRs that 24 waves allow since the bias row moved to LDS (K = 96: 76-78; K = 128 spills: 4 waves).
-    if constexpr (NW == RG_WAVES && ((KS <= 4 && !STD && EPI == EPI_GELU_BWD) || (KS <= 3 && STD))) {
-        if (RG_SMALL_K_WAVES == 8)
-            return launch_rg<KS, STD, EPI, 8>(x, res, sum_out, mean, rstd, xhat_out, wt, bias, pre_in, y, pre_out, M, N, ldx, ldy,
-                                              eps, st, xscale, rps);
-    }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_kernel<KS, STD, EPI, NW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    const int ny = (N + C::TN - 1) / C::TN;
-    const int64_t row_blocks = ((M + 15) / 16 + NW - 1) / NW;
+    if (((KS <= 4 && !STD && EPI == EPI_GELU_BWD) || (KS <= 3 && STD)) && RG_SMALL_K_WAVES == 8) return 8;
+    return RG_WAVES;
+}
+
+int rg_decide(int KS, bool STD, int EPI, int64_t M, int N, ClvRowgemmPlan* pl) {
+    if (rg_lds_bytes(KS, EPI, RG_WAVES) > 160 * 1024) return CLV_ERR_UNSUPPORTED;
+    const int NW = rg_waves(KS, STD, EPI);
+    const size_t lds = rg_lds_bytes(KS, EPI, NW);
+    if (lds > 160 * 1024) return CLV_ERR_UNSUPPORTED;
+    const int TN = (KS <= 12 && KS > 4) ? 128 : 64;
+    const int ny = (N + TN - 1) / TN;
+    const int64_t ntiles = (M + 15) / 16;
+    const int64_t row_blocks = (ntiles + NW - 1) / NW;
     // persistent workgroups, exactly as many as are resident at once (LDS-limited): every workgroup loads its weight
     // tile (up to 100 KB) ONCE and then streams its share of the rows — with more workgroups than that the tile
     // reload dominates (measured: 1536 workgroups of 2 row tiles per wave ran fc2 at a third of this)
@@ -261,7 +258,33 @@ int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float*
     gx *= RG_ROW_SLICE_MULT;
     if (gx < 8) gx = 8;
     if (gx > row_blocks) gx = row_blocks;
-    rowgemm_kernel<KS, STD, EPI, NW><<<dim3((unsigned)(gx * ny)), dim3(64 * NW), lds, st>>>(
+    pl->TN = TN;
+    pl->waves = NW;
+    pl->ny = ny;
+    pl->gx = (int32_t)gx;
+    pl->lds_bytes = (int32_t)lds;
+    pl->trips = (int32_t)((ntiles + gx * NW - 1) / (gx * NW));
+    return CLV_OK;
+}
+
+// ---- "launch": the instantiation whose wave count rg_waves names, on the grid and LDS size of the record
+template <int KS, bool STD, int EPI>
+int launch_rg(const void* x, const void* res, void* sum_out, float* mean, float* rstd, void* xhat_out, const void* wt,
+              const float* bias, const void* pre_in, void* y, void* pre_out, int64_t M, int N, int ldx, int ldy,
+              float eps, hipStream_t st, const float* xscale = nullptr, int rps = 1) {
+    constexpr int NW = rg_waves(KS, STD, EPI);
+    ClvRowgemmPlan pl;
+    const int rc = rg_decide(KS, STD, EPI, M, N, &pl);
+    if (rc != CLV_OK) return rc;
+    static_assert(RGCfg<KS>::TN == ((KS <= 12 && KS > 4) ? 128 : 64), "rg_decide and RGCfg disagree on the column tile");
+    if (pl.waves != NW || pl.TN != RGCfg<KS>::TN) return CLV_ERR_LAUNCH;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_kernel<KS, STD, EPI, NW>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
+        attr = true;
+    }
+    rowgemm_kernel<KS, STD, EPI, NW><<<dim3((unsigned)((int64_t)pl.gx * pl.ny)), dim3(64 * pl.waves), (size_t)pl.lds_bytes, st>>>(
         (const bf16_t*)x, (const bf16_t*)res, (bf16_t*)sum_out, mean, rstd, (bf16_t*)xhat_out, (const bf16_t*)wt, bias,
         (const bf16_t*)pre_in, (bf16_t*)y, (bf16_t*)pre_out, M, N, ldx, ldy, eps, xscale, rps > 0 ? rps : 1);
     return clv_check_launch();
@@ -296,6 +319,14 @@ extern "C" int clv_rowgemm_supported(int32_t N, int32_t K, int32_t standardise) 
     if (!ok) return 0;
     if (standardise && ks > 8) return 0;
     return 1;
+}
+
+extern "C" int clv_rowgemm_plan(int64_t M, int32_t N, int32_t K, int32_t standardise, int32_t epilogue, ClvRowgemmPlan* out) {
+    if (!out || M <= 0 || !clv_rowgemm_supported(N, K, standardise)) return CLV_ERR_ARG;
+    // the (prologue, epilogue) pairs dispatch_rg knows
+    if (standardise ? (epilogue != EPI_NONE && epilogue != EPI_GELU) : (epilogue != EPI_NONE && epilogue != EPI_GELU_BWD))
+        return CLV_ERR_UNSUPPORTED;
+    return rg_decide(K / 32, standardise != 0, epilogue, M, N, out);
 }
 
 static int rowgemm_impl(const void* x, const void* res, void* sum_out, float* mean, float* rstd, void* xhat_out,

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CLV_ABI_VERSION 18
+#define CLV_ABI_VERSION 19
 #define CLV_ERR_ARG (-1)
 #define CLV_ERR_UNSUPPORTED (-2)
 #define CLV_ERR_LAUNCH (-3)
@@ -358,6 +358,18 @@ int clv_rowgemm_xs(const void* x, const void* res, void* sum_out, float* mean, f
                    const void* wt, const float* bias, const void* pre_in, void* y, void* pre_out, int64_t M, int32_t N,
                    int32_t K, int32_t ldx, int32_t ldy, int32_t standardise, int32_t epilogue, float eps,
                    const float* xscale, int32_t rows_per_sample, void* stream);
+/* What clv_rowgemm / clv_rowgemm_xs launch for a shape (host only, no GPU needed; ABI 19).  The launch dispatches on the same
+ * record, so the entry cannot drift from it.  Returns CLV_ERR_ARG / CLV_ERR_UNSUPPORTED as clv_rowgemm does for the same
+ * M, N, K, standardise and epilogue, and CLV_ERR_ARG for out == NULL.
+ *   TN         columns of the weight tile a workgroup keeps in LDS;  ny = ceil(N / TN) column tiles
+ *   waves      per workgroup (4, 8 or 12): a function of K, prologue and epilogue alone
+ *   gx         persistent row slices; the grid is gx * ny workgroups
+ *   lds_bytes  dynamic LDS of the launch
+ *   trips      ceil(ceil(M / 16) / (gx * waves)): 16-row tiles the busiest wave walks; >= 2 means the wave loop repeats */
+typedef struct ClvRowgemmPlan {
+    int32_t TN, waves, ny, gx, lds_bytes, trips;
+} ClvRowgemmPlan;
+int clv_rowgemm_plan(int64_t M, int32_t N, int32_t K, int32_t standardise, int32_t epilogue, ClvRowgemmPlan* out);
 
 /* ------------------------------------------------------------------ the MLP half of a stage-0 block as one kernel each way
  * (round 6) norm2 + Mlp + the residual add in front of them — swin_transformer_3d.py:482-483 (norm2, mlp), :262-268
@@ -383,6 +395,16 @@ int clv_mlp_fused_bwd(const void* tsum, const float* mean, const float* rstd, co
                       const void* w1f, const float* b1f, const void* w2t, void* da, void* dres, void* act_out,
                       void* dpre_out, void* xhat_out, int64_t M, int32_t C, int32_t hidden, const float* xscale,
                       int32_t rows_per_sample, void* stream);
+/* How clv_mlp_fused_fwd / _bwd cut M rows into workgroups (host only; ABI 19); the kernels take their row ranges from the
+ * same helper.  CLV_ERR_ARG for M <= 0 or out == NULL.
+ *   grid                  workgroups, each with a contiguous range of 16-token tiles
+ *   tiles_min, tiles_max  the smallest / largest tile count of a workgroup
+ *   trips                 groups of two tiles per wave in the fullest workgroup (8 waves); >= 2: the forward's row prefetch runs
+ *   half_group            1: some workgroup has an odd tile count, so its last group runs the one-tile body */
+typedef struct ClvMlpFusedPlan {
+    int32_t grid, tiles_min, tiles_max, trips, half_group;
+} ClvMlpFusedPlan;
+int clv_mlp_fused_plan(int64_t M, ClvMlpFusedPlan* out);
 
 /* db[n] += sum_m dy[m][n] (bf16 dy, row stride ld; N, ld multiples of 8): the bias gradient of the
  * library-GEMM Linear layers (BERT / fusion / MLM head), ACCUMULATED into db. */
