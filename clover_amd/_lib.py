@@ -195,6 +195,8 @@ SIGNATURES = {
     'clv_ema_update': (C.c_int, [_p, _i32, _i32, C.c_double, _p]),
     'clv_ema_swap': (C.c_int, [_p, _i32, _i32, _p]),
     'clv_grad_report': (C.c_int, [_p, _i32, _p, _i32, _i32, _p, _p, _i32, _p]),
+    'clv_act_report': (C.c_int, [_p, _i64, _i32, _p, _p]),
+    'clv_act_report_latch': (C.c_int, [_p, _p, _p, _i32, _p]),
     'clv_quant_fp8_rows': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _i64, _p]),
     'clv_gemm_nt_fp8_supported': (C.c_int, [_i64, _i32, _i32]),
     'clv_gemm_nt_fp8': (C.c_int, [_p] * 7 + [_i64, _i32, _i32, _i64, _i64, _i64, _i32, _p]),

@@ -20,6 +20,7 @@ DefaultOptimizerConstructor + AdamW (pretrain_webvid_cc3m.py:129-137), Fp16Optim
 * ``ema_enable`` / ``ema_update`` / ``ema_swap``: the reference's ``ema_hook`` (mmaction/core/hooks/ema.py) — an fp32 moving
   average of the weights in a slab of its own per segment, updated and exchanged with the weights by one HIP launch each.
 """
+import contextlib
 import inspect
 import math
 
@@ -239,12 +240,177 @@ class _Capture:
         self.prepacked = prepacked                             # buckets whose wire copy the backward graphs write
 
 
+# Methods through which the step graph enters a module WITHOUT nn.Module.__call__ (the pending-residual form of the Swin
+# blocks and patch mergings, the patch embedding's token layouts, the projection head's two towers): torch's forward hooks do
+# not see those calls, so the activation report wraps them on the watched instances.
+ACT_ENTRY_METHODS = ('forward_pending', 'tokens', 'tokens_stacked', 'forward_text', 'forward_vision')
+
+
+def default_watched_modules(model):
+    """The block-level modules the activation report watches unless told otherwise, as named_modules() names: the patch
+    embedding, every Swin block, every patch merging and the Swin final norm; the embeddings module and every transformer
+    layer of the text and the fusion encoder; the fusion encoder's input projection (``fc_in`` where the widths differ, and
+    the ``norm`` that closes the projection); every head that is a direct child of the recognizer."""
+    from .backbones.bert_layers import BertEmbeddings, BertLayer
+    from .backbones.cross_transformer import CrossModalTransformerFromPretrained
+    from .backbones.swin_transformer_3d import PatchEmbed3D, PatchMerging, SwinTransformer3D, SwinTransformerBlock3D
+    names = []
+    for name, mod in model.named_modules():
+        if isinstance(mod, (PatchEmbed3D, SwinTransformerBlock3D, PatchMerging, BertEmbeddings, BertLayer)):
+            names.append(name)
+        elif isinstance(mod, SwinTransformer3D):
+            names.append(f'{name}.norm')
+        elif isinstance(mod, CrossModalTransformerFromPretrained):
+            names += [f'{name}.{c}' for c in ('fc_in', 'norm') if hasattr(mod, c)]
+    heads_pkg = __name__.rsplit('.', 1)[0] + '.heads'
+    names += [name for name, child in model.named_children() if type(child).__module__.startswith(heads_pkg)]
+    return names
+
+
+class _ActivationWatch:
+    """The host side of the activation report (csrc/act_report.hip): one 16-byte device record per watched module, folded
+    into by one clv_act_report launch per floating tensor of the module's output — inside the step's hipGraphs, because
+    the hooks fire while the graphs are captured.  ``on`` gates every launch: the engine sets it only around the forward
+    passes it drives itself, so an evaluation or any other caller of the model leaves the table alone."""
+
+    def __init__(self, model, spec, device):
+        import fnmatch
+        modules = dict(model.named_modules())
+        wanted = set(n for n in default_watched_modules(model) if n in modules)
+        patterns = list(spec.get('modules') or []) if isinstance(spec, dict) else []
+        self._asked = {}                       # pattern -> the modules it added
+        for pat in patterns:
+            hit = [n for n in modules if n and fnmatch.fnmatchcase(n, pat)]
+            if not hit:
+                raise ValueError(f'activation_report: the pattern {pat!r} matches no module of {type(model).__name__}')
+            wanted.update(hit)
+            self._asked[pat] = hit
+        self.watched = [n for n in modules if n in wanted]      # registration order, until the dry run has given the forward order
+        self.names, self.slot, self.numel = [], {}, {}          # forward order: slot i belongs to names[i]
+        self.live, self.latched = ops.act_report_new(len(self.watched), device)
+        self.on, self.discover, self.stale = False, True, True
+        self._depth = {}
+        self._fired, self._clock = {}, 0
+        self._undo = []
+        for name in self.watched:
+            self._install(name, modules[name])
+
+    def _install(self, name, mod):
+        def enter(*_a, **_k):
+            self._depth[name] = self._depth.get(name, 0) + 1
+
+        def leave(output):
+            d = self._depth[name] = self._depth.get(name, 1) - 1
+            if d == 0 and self.on:
+                self.scan(name, output)
+
+        self._undo.append(mod.register_forward_pre_hook(enter).remove)
+        self._undo.append(mod.register_forward_hook(lambda _m, _i, output: leave(output)).remove)
+        for meth in ACT_ENTRY_METHODS:
+            inner = getattr(mod, meth, None)
+            if inner is None or not callable(inner):
+                continue
+
+            def entry(*a, _inner=inner, **k):
+                enter()
+                try:
+                    output = _inner(*a, **k)
+                except BaseException:
+                    self._depth[name] -= 1
+                    raise
+                leave(output)
+                return output
+            object.__setattr__(mod, meth, entry)
+            self._undo.append(lambda _mod=mod, _meth=meth: object.__delattr__(_mod, _meth))
+
+    def remove(self):
+        for undo in self._undo:
+            undo()
+        self._undo = []
+
+    @staticmethod
+    def tensors(output):
+        """Every floating HIP tensor of a module's output: a tensor, or tuples / lists / dicts of them."""
+        if torch.is_tensor(output):
+            return [output] if output.is_cuda and output.is_floating_point() else []
+        if isinstance(output, dict):
+            return [t for o in output.values() for t in _ActivationWatch.tensors(o)]
+        if isinstance(output, (tuple, list)):
+            return [t for o in output for t in _ActivationWatch.tensors(o)]
+        return []
+
+    def scan(self, name, output):
+        i = self.slot.get(name)
+        seen, ts = set(), []
+        for t in self.tensors(output):         # a forked output hands the same storage out twice: scanned once
+            key = (t.data_ptr(), t.dtype, tuple(t.shape), t.stride())
+            if key not in seen:
+                seen.add(key)
+                ts.append(t)
+        if self.discover:                      # the constructor's dry run: note who fires when, launch nothing yet
+            if ts:
+                self._fired[name] = self._tick()
+                self.numel.setdefault(name, sum(t.numel() for t in ts))
+            return
+        if i is None:
+            return
+        for t in ts:
+            t = t.detach()
+            if t.dtype not in (torch.float32, ops.BF16):
+                t = t.float()
+            ops.act_report(t if t.is_contiguous() else t.contiguous(), self.live[i])
+
+    def _tick(self):
+        self._clock += 1
+        return self._clock
+
+    def end_discovery(self):
+        """The dry run is through: the slots in forward order — the order in which the hooks fired.  A module the step enters
+        more than once (the projection head: the text tower's rows early, the video tower's behind the video encoder) stands
+        where its LAST call is, so that no row can precede a module whose output it consumed; a watched module the step
+        never enters has no slot."""
+        self.discover = False
+        for pat, hit in self._asked.items():   # a request that can never report anything is refused, not dropped
+            if not any(n in self._fired for n in hit):
+                self.remove()
+                raise ValueError(f'activation_report: the step never calls a module matching {pat!r} ({", ".join(hit[:3])}'
+                                 f'{", ..." if len(hit) > 3 else ""}): its parent runs it inside a fused kernel, or the '
+                                 'recognizer does not use it; watch the parent instead')
+        self.names = sorted(self._fired, key=self._fired.get)
+        self.slot = {name: i for i, name in enumerate(self.names)}
+
+    def begin_step(self):
+        """Ahead of an optimizer step's first forward: the records of the last step make room.  An eager fill on the current
+        stream (the forward graph is replayed behind it), once per optimizer step however many forwards that step has."""
+        self._depth.clear()
+        if self.stale:
+            self.live.zero_()
+            self.stale = False
+
+    def rows(self, rec, offending_only):
+        return [(name, self.numel[name], int(c), int(nf), float(mx))
+                for name, nf, mx, c in zip(self.names, rec['nonfinite'].tolist(), rec['max_abs'].tolist(), rec['calls'].tolist())
+                if nf or not offending_only]
+
+
 class CloverEngine:
     def __init__(self, model, sample_batch, lr=5e-5, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.005,
                  paramwise_cfg=None, grad_clip=15.0, max_iters=100000, warmup_iters=0, min_lr_ratio=1e-3,
-                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None, virtual_ranks=1, overflow_report=False):
+                 warmup_ratio=1e-3, bucket_mb=64, loss_scale=None, virtual_ranks=1, overflow_report=False,
+                 activation_report=False):
         self.model = model
         self.virtual_ranks = int(virtual_ranks)
+        # activation_report=True (or dict(modules=[fnmatch patterns over named_modules() names], added to the default
+        # block-level list): every forward pass the engine drives folds each watched module's output into a device record —
+        # non-finite count, largest finite magnitude — with one clv_act_report launch per output tensor, captured in the
+        # forward graphs.  activation_stats() reads the table (the headroom below the 16-bit limit); with overflow_report=True
+        # as well a skipped step latches it and overflow_report() names the FIRST module whose output was non-finite.  Off
+        # (the default): no hook, no launch, no buffer.
+        if activation_report is not False and activation_report is not True and not isinstance(activation_report, dict):
+            raise ValueError(f'activation_report must be True, False or dict(modules=[...]), got {activation_report!r}')
+        if isinstance(activation_report, dict) and set(activation_report) - {'modules'}:
+            raise ValueError(f'activation_report: unknown keys {sorted(set(activation_report) - {"modules"})} (known: modules)')
+        self._act = None                       # the _ActivationWatch, built below once the device is known
         # overflow_report=True: every optimizer step also launches clv_grad_report in its "on skip" mode over the gradients —
         # two kernels per slab that return at once unless the step was skipped; overflow_report() then names the
         # parameters that held the non-finite values.  Off (the default): the step launches what it always launched.
@@ -320,7 +486,14 @@ class CloverEngine:
 
         # ---- dry run: which parameters does the step graph actually reach?
         model.zero_grad(set_to_none=True)
-        out = model.train_step(sample_batch, None)
+        if activation_report is not False:
+            # hooked BEFORE the dry run: the order in which the hooks fire there is the table's forward order
+            # (_ActivationWatch.end_discovery), and every forward graph captured later holds the scans
+            self._act = _ActivationWatch(model, activation_report, device)
+        with self._act_forward():
+            out = model.train_step(sample_batch, None)
+        if self._act is not None:
+            self._act.end_discovery()
         out['loss'].backward()
         used = [(n, p) for n, p in model.named_parameters() if p.requires_grad and p.grad is not None]
         name_of = {id(p): n for n, p in model.named_parameters()}
@@ -579,11 +752,14 @@ class CloverEngine:
         gradient reducer's hook calibration and leaves weights, Adam moments, step counts and the LR index untouched
         (gradients are zeroed again)."""
         self._ft.done.clear()
-        out = self.model.train_step(batch, None)
+        self._act_begin_step()
+        with self._act_forward():
+            out = self.model.train_step(batch, None)
         self._backward(lambda: out['loss'].backward())
         self.finish_backward()
         self._stale_cleared = False
         self._clear_all()
+        self._act_end_step()
         return out
 
     def step(self, batch):
@@ -610,11 +786,14 @@ class CloverEngine:
         self.reducer.begin_step()
         if self.graph is not None:
             self._select(batch)
+            self._act_begin_step()             # behind a first-sight capture, whose warm-up passes fold into the table too
             out = self._graphed_forward_backward(batch)
         else:
             self.reducer.prepacked = frozenset()
             self._ft.done.clear()
-            out = self.model.train_step(batch, None)
+            self._act_begin_step()
+            with self._act_forward():
+                out = self.model.train_step(batch, None)
             self._backward(lambda: out['loss'].backward())
         self.finish_backward()
         return out
@@ -657,6 +836,7 @@ class CloverEngine:
         graphed = self.graph is not None
         if graphed:
             self._select(batches[0])
+        self._act_begin_step()                 # all 2k - 1 forwards of the step fold into the same records
         model, cap = self.model, self._active
         drop_ctr = ops._dropout_counter(self._device)
 
@@ -676,7 +856,7 @@ class CloverEngine:
                         v.copy_(b[name], non_blocking=True)
                 self.graph.replay()
                 return cap.emb, cap.mlm
-            with torch.enable_grad() if grad else torch.no_grad():
+            with torch.enable_grad() if grad else torch.no_grad(), self._act_forward():
                 return model.encode(b['imgs'], **{name: b[name] for name in self._encode_keys})
 
         def backward(live, demb, dmlm):
@@ -922,7 +1102,8 @@ class CloverEngine:
                 vcuts = [] if cut_ok else None
                 tcuts = [] if text_ok else None
                 self._ft.done.clear()
-                emb, mlm = encode(vcuts, tcuts)
+                with self._act_forward():
+                    emb, mlm = encode(vcuts, tcuts)
                 self._backward(lambda: torch.autograd.backward(*roots(emb, mlm, torch.zeros_like(emb),
                                                                       torch.zeros_like(mlm) if mlm is not None else None)))
                 if vcuts:
@@ -941,8 +1122,8 @@ class CloverEngine:
         # thread_local: RCCL's watchdog thread (W > 1) keeps polling events while we capture
         vcuts = [] if cut_ok else None
         tcuts = [] if text_ok else None
-        with torch.cuda.graph(gf, capture_error_mode='thread_local'):
-            emb, mlm = encode(vcuts, tcuts)
+        with torch.cuda.graph(gf, capture_error_mode='thread_local'), self._act_forward():
+            emb, mlm = encode(vcuts, tcuts)                # (the watched modules' scans are nodes of this graph)
         demb = torch.zeros_like(emb)
         dmlm = torch.zeros_like(mlm) if mlm is not None else None
         # Data-parallel jobs: the bf16 wire copy of every bucket is written INSIDE the backward graph that completes its
@@ -982,6 +1163,7 @@ class CloverEngine:
             raise RuntimeError('fused gradient norm: the captured backward gives a first-touch sink two gradients; build the '
                                'engine with CLOVER_FUSED_NORM=0')
         cap.graph_loss, cap.loss_io = self._capture_loss_graph(cap)
+        self._act_end_step()                       # the warm-up passes folded into the table: the next step starts clean
         # published whole and last: a capture that raised has left the engine's geometries as they were
         sig = self._signature(batch)
         self._captures[sig] = cap
@@ -1070,6 +1252,9 @@ class CloverEngine:
         ops.optim_prep(self.sumsq, self.optim_state, self.betas[0], self.betas[1],
                        self.grad_clip if self.grad_clip else 0.0, gscale,
                        slots=self.sumsq[16:] if self._norm_tables is not None else None)
+        if self._act is not None and self._overflow_report:
+            # right behind the skip decision, where the gradient report goes: a skipped step keeps its forward records
+            ops.act_report_latch(self.optim_state, self._act.live, self._act.latched, len(self._act.names))
         for seg, g in zip(self.segments, grads):
             ops.adamw_step_dev(seg.flat_p, g, seg.exp_avg, seg.exp_avg_sq, seg.shadow, self.optim_state,
                                lr * seg.lr_mult, self.betas[0], self.betas[1], self.eps, seg.weight_decay)
@@ -1078,6 +1263,7 @@ class CloverEngine:
             for g, tab, out in zip(grads, self._grad_report_tables(), self._report_out):
                 ops.grad_report(g, tab, self.optim_state, out, 0)
         self.zero_grads()
+        self._act_end_step()
         self.last_lr = lr
 
     # ------------------------------------------------------------------ overflow report (csrc/grad_report.hip)
@@ -1119,7 +1305,48 @@ class CloverEngine:
             raise RuntimeError('overflow_report(): this engine was built without overflow_report=True, so its optimizer '
                                'steps do not take the report; pass CloverEngine(..., overflow_report=True) (tools/train.py: '
                                'the config key overflow_report = dict(interval=...))')
-        return self._report_rows(self._report_out, offending_only=True)
+        rep = self._report_rows(self._report_out, offending_only=True)
+        if rep is not None and self._act is not None:
+            act = self._act
+            rows = act.rows(ops.act_report_read(act.latched, len(act.names), latched=True), offending_only=True)
+            rep['activations'] = dict(first=rows[0][0] if rows else None, rows=rows)
+        return rep
+
+    # ------------------------------------------------------------------ activation report (csrc/act_report.hip)
+    @contextlib.contextmanager
+    def _act_forward(self):
+        """Around a forward pass the engine drives: the watched modules' hooks launch only in here."""
+        act = self._act
+        if act is None:
+            yield
+            return
+        act.on = True
+        try:
+            yield
+        finally:
+            act.on = False
+
+    def _act_begin_step(self):
+        if self._act is not None:
+            self._act.begin_step()
+
+    def _act_end_step(self):
+        if self._act is not None:
+            self._act.stale = True
+
+    def activation_stats(self):
+        """The headroom view (host sync): ``dict(limit, rows)`` with one row ``(name, numel_per_call, calls, nonfinite,
+        max_abs)`` per watched module, in forward order, from the live table as it stands — the forward passes of the last
+        optimizer step (the table is cleared ahead of a step's first forward: an eager fill issued by the engine, not a node
+        of the graphs).  ``max_abs`` is the largest finite magnitude the module's output held, ``limit`` the largest finite
+        value of the build's 16-bit type (65504 in the fp16 build).  Needs ``CloverEngine(..., activation_report=True)``."""
+        if self._act is None:
+            raise RuntimeError('activation_stats(): this engine was built without activation_report=True, so its forward '
+                               'passes do not scan their outputs; pass CloverEngine(..., activation_report=True) (tools/'
+                               'train.py: the config key overflow_report = dict(interval=..., activations=True))')
+        act = self._act
+        rows = act.rows(ops.act_report_read(act.live, len(act.names), latched=False), offending_only=False)
+        return dict(limit=float(torch.finfo(ops.BF16).max), rows=rows)
 
     def grad_stats(self):
         """The same rows for EVERY parameter of the gradients as they stand (host sync): call it between

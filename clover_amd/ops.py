@@ -2673,6 +2673,70 @@ def grad_report_read(out, table):
                 max_abs=f[a + 1:b:4].clone(), sumsq=f[a + 2:b:4].clone(), norm=f[a + 3:b:4].clone())
 
 
+# --------------------------------------------------------------------------- activation report (csrc/act_report.hip)
+ACT_REPORT_SLOT_WORDS = 4                 # include/clover_hip.h: CLV_ACT_REPORT_SLOT_BYTES
+
+
+def act_report_new(n_slots, device):
+    """Zeroed activation-report buffers for ``n_slots`` records -> (live, latched), int32 words: ``live`` is the table
+    act_report folds into (row i = slot i: {nonfinite, max_abs bits, calls, 0}), ``latched`` a header plus a copy of it."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError('clover_amd ops run only on a HIP device (MI355X); there is no CPU fallback — '
+                           'got device %s' % device)
+    if int(n_slots) < 0:
+        raise ValueError(f'act_report_new: n_slots {n_slots}')
+    live = torch.zeros(max(int(n_slots), 1), ACT_REPORT_SLOT_WORDS, dtype=torch.int32, device=device)
+    latched = torch.zeros(GRAD_REPORT_HEADER_WORDS + ACT_REPORT_SLOT_WORDS * int(n_slots), dtype=torch.int32, device=device)
+    return live, latched
+
+
+def act_report(t, slot_view):
+    """Fold the contiguous fp32 / 16-bit tensor ``t`` into one record (``slot_view``: a row of act_report_new's live
+    table): nonfinite += its NaN / inf count, max_abs = max(max_abs, largest finite |t|), calls += 1.  One launch on the
+    current stream, no host sync, capturable; integer atomics only, so the record does not depend on block order."""
+    _need_gpu(t, slot_view)
+    if t.dtype not in (torch.float32, BF16) or not t.is_contiguous():
+        raise ValueError(f'act_report: t must be a contiguous fp32 or {BF16} tensor, got {t.dtype}'
+                         f'{"" if t.is_contiguous() else " (not contiguous)"}')
+    if slot_view.dtype != torch.int32 or slot_view.numel() != ACT_REPORT_SLOT_WORDS or not slot_view.is_contiguous():
+        raise ValueError(f'act_report: slot_view is one record of {ACT_REPORT_SLOT_WORDS} int32 words (a row of act_report_new)')
+    n = t.numel()
+    with _Timed('act_report_kernel', 2 * n, t.element_size() * n):
+        check(_lib.lib().clv_act_report(_ptr(t) if n else None, n, 1 if t.dtype == BF16 else 0, _ptr(slot_view), _stream()),
+              'clv_act_report')
+
+
+def act_report_latch(state, live, latched, n_slots):
+    """Behind optim_prep: if ``state`` says the step was skipped, ``latched`` = header {t, skipped, loss_scale of those
+    gradients, n_slots} + a copy of the first ``n_slots`` records of ``live``; otherwise nothing is written.  One launch."""
+    _need_gpu(state, live, latched)
+    n_slots = int(n_slots)
+    if live.dtype != torch.int32 or not live.is_contiguous() or live.numel() < ACT_REPORT_SLOT_WORDS * n_slots:
+        raise ValueError(f'act_report_latch: live must be a contiguous int32 table of >= {n_slots} records')
+    words = GRAD_REPORT_HEADER_WORDS + ACT_REPORT_SLOT_WORDS * n_slots
+    if latched.dtype != torch.int32 or not latched.is_contiguous() or latched.numel() < words:
+        raise ValueError(f'act_report_latch: latched must be a contiguous int32 tensor of >= {words} words (act_report_new)')
+    if state.dtype != torch.int32 or state.numel() * 4 < OPTIM_STATE_BYTES:
+        raise ValueError('act_report_latch: state is the int32 record of optim_state_new')
+    check(_lib.lib().clv_act_report_latch(_ptr(state), _ptr(live), _ptr(latched), n_slots, _stream()), 'clv_act_report_latch')
+
+
+def act_report_read(buf, n_slots, latched):
+    """Host copy (syncs) of act_report_new's ``latched`` buffer (latched=True) or ``live`` table (False): dict(t, skipped,
+    loss_scale, n_slots — all None for the live table; n_slots == 0 in a latched buffer: nothing was latched yet —
+    nonfinite, max_abs, calls: one CPU tensor each with an entry per slot; max_abs fp32)."""
+    raw = buf.detach().cpu().reshape(-1)
+    n_slots = int(n_slots)
+    head = dict(t=None, skipped=None, loss_scale=None, n_slots=None)
+    a = 0
+    if latched:
+        head = dict(t=int(raw[0]), skipped=int(raw[1]), loss_scale=float(raw.view(torch.float32)[2]), n_slots=int(raw[3]))
+        a = GRAD_REPORT_HEADER_WORDS
+    rec = raw[a:a + ACT_REPORT_SLOT_WORDS * n_slots].reshape(n_slots, ACT_REPORT_SLOT_WORDS)
+    return dict(head, nonfinite=rec[:, 0].clone(), max_abs=rec[:, 1].clone().view(torch.float32), calls=rec[:, 2].clone())
+
+
 # --------------------------------------------------------------------------- video QA / fill-in-the-blank (csrc/qa.hip)
 QA_MASK_ID = 103         # BERT [MASK]: the answer row of fill-in-the-blank (multimodal_transformer_finetune.py:100-102)
 

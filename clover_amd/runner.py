@@ -224,7 +224,10 @@ class OverflowHook(Hook):
     look, the engine's overflow report (``engine.overflow_report()``: needs ``CloverEngine(overflow_report=True)``) is
     printed: the ``top`` parameters by count of non-finite gradient elements, then by largest finite magnitude.  With
     ``max_consecutive_skips = N`` a run of N skipped steps in a row raises ``RuntimeError`` with the scale and those
-    parameters — a static scale that overflows skips every step from then on, and says nothing.  The run is derived from the
+    parameters — a static scale that overflows skips every step from then on, and says nothing.  When the engine also
+    scans its forward outputs (``CloverEngine(activation_report=True)``: the report has ``activations``) the text gains a
+    forward line — the first watched module whose output was non-finite, or that all were finite — and the error names
+    that module: a forward overflow makes EVERY gradient non-finite, and no loss scale cures it.  The run is derived from the
     ``skipped`` and ``calls`` deltas between two looks: every step of the window skipped extends it, none skipped ends it;
     a window with both (possible with ``interval > 1`` only) restarts it from what is known, the last step."""
 
@@ -253,7 +256,18 @@ class OverflowHook(Hook):
                  f'{report["loss_scale"]:g}; {len(report["rows"])} parameter(s) with non-finite gradients, top {len(rows)}:']
         lines += [f'  {name}: {nf} of {numel} non-finite, max |g| {mx:.4g}, norm {norm:.4g} over the finite ones'
                   for name, numel, nf, mx, norm in rows]
+        if 'activations' in report:            # an engine with activation_report=True: where the FORWARD pass broke, if it did
+            lines.append(self.describe_forward(report['activations']))
         return '\n'.join(lines)
+
+    @staticmethod
+    def describe_forward(activations):
+        rows = activations['rows']
+        if activations['first'] is None:
+            return 'forward outputs all finite: the overflow arose in the backward pass or the loss'
+        name, numel, calls, nf, _ = rows[0]
+        return (f'forward: first non-finite output at {name} ({nf} of {numel * calls}), {len(rows) - 1} watched modules '
+                'downstream')
 
     def after_train_iter(self, runner):
         self._steps += 1
@@ -274,9 +288,11 @@ class OverflowHook(Hook):
             self.printer(self.describe(report))
         if self.max_consecutive_skips is not None and self.run_of_skips >= self.max_consecutive_skips:
             names = ', '.join(r[0] for r in self.top_rows(report, self.top)) if report else 'no report'
+            first = ((report or {}).get('activations') or {}).get('first')
             raise RuntimeError(f'{self.run_of_skips} optimizer steps in a row were skipped for non-finite gradients at '
                                f'loss_scale {st["loss_scale"]:g} (max_consecutive_skips={self.max_consecutive_skips}); '
-                               f'parameters with non-finite gradients: {names}')
+                               f'parameters with non-finite gradients: {names}' + (
+                                   f'; first non-finite forward output: {first}' if first else ''))
 
 
 class CheckpointHook(Hook):

@@ -657,6 +657,35 @@ int clv_ema_swap(const void* table, int32_t n_entries, int32_t n_blocks, void* s
 int clv_grad_report(const void* buf, int32_t elem, const void* table, int32_t n_params, int32_t n_chunks,
                     const void* state, void* report, int32_t mode, void* stream);
 
+/* ------------------------------------------------------------------ activation report (csrc/act_report.hip)
+ * Which forward output went non-finite first.  The reference's overflow check looks at gradients only
+ * (LossScaler.has_overflow / _has_inf_or_nan, mmaction/core/hooks/fp16_utils.py:328-349) and its hook announces the
+ * overflow without a place (mmcv_Fp16OptimizerHook.py:123-141); an fp16 forward value above 65504 is stored as inf, every
+ * gradient behind it is non-finite, and the gradient report above then lists the whole model.  These two entries keep one
+ * 16-byte record per watched forward output, on the device and inside the step's hipGraphs.
+ *
+ * clv_act_report folds x into the record at slot:
+ *   x      count elements, elem = CLV_GRAD_REPORT_F32 or CLV_GRAD_REPORT_HALF (the library's 16-bit type), naturally
+ *          aligned; may be NULL when count == 0, which is legal and only bumps `calls`
+ *   slot   (16-byte aligned) {int32 nonfinite; uint32 max_abs; int32 calls; int32 zero}: nonfinite += the number of NaN and
+ *          +-inf elements, max_abs = max(max_abs, bits of the largest FINITE |x| as fp32) — ordered like an integer, as in
+ *          the gradient report's records — and calls += 1.  The caller clears the record (16 zero bytes).
+ * One launch: a bounded grid with a grid-stride loop, 16-byte loads from the first 16-byte boundary on, the elements before
+ * it and behind the last full vector one by one, a reduction over the wave and the block, then at most one 32-bit integer
+ * atomicAdd and one atomicMax per block.  Integer add and max commute: the record is a pure function of what was folded in.
+ * No float accumulation.  count > INT32_MAX: CLV_ERR_UNSUPPORTED; NULL / misaligned arguments, count < 0, an unknown elem:
+ * CLV_ERR_ARG.
+ *
+ * clv_act_report_latch, for use behind clv_optim_prep: when state.skip == 0 it returns at once and `latched` keeps every
+ * byte (mode 0 of clv_grad_report); on a skipped step it writes {int32 t, skipped; float loss_scale (the one the gradients
+ * carried: state.grad_loss_scale); int32 n_slots; 4 x int32 0} — the gradient report's header — followed by a copy of the
+ * n_slots records at `live`.  latched: CLV_GRAD_REPORT_HEADER_BYTES + CLV_ACT_REPORT_SLOT_BYTES * n_slots bytes; live and
+ * latched 16-byte aligned.  One small launch.
+ * Both are plain launches on `stream`: capturable, they allocate nothing and synchronise nothing. */
+#define CLV_ACT_REPORT_SLOT_BYTES 16
+int clv_act_report(const void* x, int64_t count, int32_t elem, void* slot, void* stream);
+int clv_act_report_latch(const void* state, const void* live, void* latched, int32_t n_slots, void* stream);
+
 /* ------------------------------------------------------------------ parity mode (fp32 storage + fp32 arithmetic)
  * The reference's CPU path is fp32 (north_star: "match the reference mmaction CPU path ... losses within 1e-3").  The
  * training path above computes on bf16 MFMA operands; these two entry points let the SAME host graph (registered modules,

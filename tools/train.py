@@ -67,7 +67,24 @@ def engine_kwargs(cfg, lr, half_f16=True):
                 # `virtual_ranks = k`: every optimizer step takes k batches whose contrastive losses see all k * B rows
                 virtual_ranks=int(cfg.get('virtual_ranks', 1) or 1),
                 # `overflow_report = dict(interval=...)`: skipped steps leave a per-parameter report (overflow_hook below)
-                overflow_report=bool(cfg.get('overflow_report')))
+                overflow_report=bool(cfg.get('overflow_report')),
+                # `overflow_report = dict(..., activations=True, modules=[...])`: the forward outputs are scanned as well and
+                # a skipped step names the first module whose output was non-finite (CloverEngine(activation_report=...))
+                activation_report=activation_report_arg(cfg))
+
+
+_ENGINE_KEYS = ('activations', 'modules')      # keys of `overflow_report` that configure the engine, not the hook
+
+
+def activation_report_arg(cfg):
+    """CloverEngine's ``activation_report`` from `overflow_report = dict(interval=..., activations=True, modules=[...])`:
+    False without ``activations``; True, or dict(modules=[...]) when extra fnmatch patterns are listed."""
+    spec = dict(cfg.get('overflow_report') or {})
+    if spec.get('modules') and not spec.get('activations'):
+        raise ValueError('overflow_report: `modules` lists extra modules for the activation report; set activations=True')
+    if not spec.get('activations'):
+        return False
+    return dict(modules=list(spec['modules'])) if spec.get('modules') else True
 
 
 def overflow_hook(cfg, rank=0):
@@ -76,7 +93,8 @@ def overflow_hook(cfg, rank=0):
     if not cfg.get('overflow_report'):
         return None
     from clover_amd.runner import OverflowHook
-    return OverflowHook(printer=print if rank == 0 else (lambda text: None), **dict(cfg.overflow_report))
+    hook_args = {k: v for k, v in dict(cfg.overflow_report).items() if k not in _ENGINE_KEYS}
+    return OverflowHook(printer=print if rank == 0 else (lambda text: None), **hook_args)
 
 
 def main():
