@@ -339,13 +339,17 @@ class BasicLayer(nn.Module):
 class PatchEmbed3D(nn.Module):
     def __init__(self, patch_size=(2, 4, 4), in_chans=3, embed_dim=96, norm_layer=None, stride=(2, 4, 4)):
         super().__init__()
-        if tuple(patch_size) != (2, 4, 4) or tuple(stride) != (2, 4, 4) or in_chans != 3:
-            raise NotImplementedError('the HIP patch-embed kernel covers patch=stride=(2,4,4), in_chans=3 '
-                                      '(every Clover / VideoSwin config)')
-        self.patch_size = tuple(patch_size)
+        self.patch_size = tuple(int(v) for v in patch_size)
+        self.stride = tuple(int(v) for v in stride)
+        # patch = stride = (2,4,4) (every Clover / VideoSwin config) runs clv_patch_embed_fwd; any other geometry the
+        # general kernel, whose supported set is stated once (clv_patch_embed_gen_supported) and refused here otherwise
+        if (self.patch_size, self.stride) != ops.PE_FAST or in_chans != 3:
+            why = ops.patch_embed_refusal(self.patch_size, self.stride, in_chans, embed_dim)
+            if why is not None:
+                raise NotImplementedError(f'PatchEmbed3D: {why}')
         self.in_chans = in_chans
         self.embed_dim = embed_dim
-        self.proj = nn.Conv3d(in_chans, embed_dim, kernel_size=patch_size, stride=stride)
+        self.proj = nn.Conv3d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.stride)
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
 
     def pad(self, x):
@@ -363,14 +367,16 @@ class PatchEmbed3D(nn.Module):
         x = self.pad(x)
         g, b = (self.norm.weight, self.norm.bias) if self.norm is not None else (None, None)
         eps = self.norm.eps if self.norm is not None else 1e-5
-        return ops.patch_embed(x, self.proj.weight, self.proj.bias, g, b, mask_token, vmask, want_clean, eps)
+        return ops.patch_embed(x, self.proj.weight, self.proj.bias, g, b, mask_token, vmask, want_clean, eps,
+                               self.patch_size, self.stride)
 
     def tokens_stacked(self, x, mask_token, vmask):
         """fp32 clip [B,3,T,H,W] -> bf16 [2B,T',H',W',C]: clean tokens, then mask-token-blended tokens."""
         x = self.pad(x)
         g, b = (self.norm.weight, self.norm.bias) if self.norm is not None else (None, None)
         eps = self.norm.eps if self.norm is not None else 1e-5
-        return ops.patch_embed_stacked(x, self.proj.weight, self.proj.bias, g, b, mask_token, vmask, eps)
+        return ops.patch_embed_stacked(x, self.proj.weight, self.proj.bias, g, b, mask_token, vmask, eps,
+                                       self.patch_size, self.stride)
 
     def forward(self, x):
         """Reference contract: [B,3,T,H,W] -> [B,C,T',H',W']."""
@@ -558,7 +564,7 @@ class SwinTransformer3D(nn.Module):
         """Reference contract: [B,3,T,H,W] -> [B,Cf,T',h,w]; with ``mask`` -> (x, w)."""
         y = self.forward_tokens(x, mask).permute(0, 4, 1, 2, 3)
         if mask is not None:
-            _, _, T, H, W = (x.shape[0], 0, (x.shape[2] + 1) // 2, (x.shape[3] + 3) // 4, (x.shape[4] + 3) // 4)
+            T, H, W = ops.patch_grid(*x.shape[2:], self.patch_embed.patch_size, self.patch_embed.stride)
             w = mask_blend_weight(mask, T, H, W).type_as(y)
             return y, w
         return y

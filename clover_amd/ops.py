@@ -1930,22 +1930,60 @@ def seq_attention(qkv, kmask, num_heads, dropout_p=0.0):
 
 
 # --------------------------------------------------------------------------- patch embed
+PE_FAST = ((2, 4, 4), (2, 4, 4))      # the geometry of clv_patch_embed_fwd (and its fp8 form); every other one: the general kernel
+_PE_REASONS = {1: 'a patch extent below 1', 2: 'stride must satisfy 1 <= stride <= patch on every axis (no gaps between patches)',
+               3: 'pt*ph*pw must be a multiple of 8 (K = 3*pt*ph*pw feeds the weight-gradient kernels in 16-byte groups)',
+               4: 'K = 3*pt*ph*pw exceeds 384', 5: 'embed_dim must be 48, 96 or 128'}
+
+
+def patch_embed_refusal(patch, stride, in_chans, Cout):
+    """None when the HIP patch-embed kernels cover the geometry, else the reason as text.  The set itself is stated once,
+    in clv_patch_embed_gen_supported (host only: no GPU needed)."""
+    if in_chans != 3:
+        return f'in_chans = {in_chans}: the kernels read 3-channel clips'
+    rc = _lib.lib().clv_patch_embed_gen_supported(*(int(v) for v in patch), *(int(v) for v in stride), int(Cout))
+    return None if rc == 0 else f'patch {tuple(patch)} stride {tuple(stride)} embed_dim {Cout}: {_PE_REASONS.get(rc, rc)}'
+
+
+def patch_grid(T, H, W, patch=PE_FAST[0], stride=PE_FAST[1]):
+    """Token grid (T', H', W') of PatchEmbed3D for a clip of T x H x W: each extent is padded up to a multiple of the
+    PATCH (PatchEmbed3D.pad, the reference's :674-680), then (extent - patch) // stride + 1."""
+    return tuple((-(-n // p) * p - p) // s + 1 for n, p, s in zip((T, H, W), patch, stride))
+
+
 class _PatchEmbed(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, stacked=False):
+    def forward(ctx, x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, stacked=False,
+                patch=PE_FAST[0], stride=PE_FAST[1]):
         _need_gpu(x, weight)
         B, Cin, T, H, W = x.shape
         Cout = weight.shape[0]
-        assert Cin == 3 and tuple(weight.shape[1:]) == (3, 2, 4, 4), 'kernel covers patch (2,4,4), 3 input channels'
+        patch, stride = tuple(int(v) for v in patch), tuple(int(v) for v in stride)
+        fast = (patch, stride) == PE_FAST
+        K = 3 * patch[0] * patch[1] * patch[2]
+        if fast:
+            assert Cin == 3 and tuple(weight.shape[1:]) == (3, 2, 4, 4), 'kernel covers patch (2,4,4), 3 input channels'
+        else:
+            why = patch_embed_refusal(patch, stride, Cin, Cout)
+            if why is not None:
+                raise NotImplementedError(f'patch embed: {why}')
+            if tuple(weight.shape[1:]) != (3,) + patch:
+                raise ValueError(f'patch embed: weight {tuple(weight.shape)} does not have the patch size {patch}')
+            if T % patch[0] or H % patch[1] or W % patch[2]:
+                raise ValueError(f'patch embed: clip {(T, H, W)} is not padded to multiples of the patch {patch} '
+                                 f'(PatchEmbed3D.pad)')
         xc = _c(x.float())
-        w2 = _c(weight.reshape(Cout, 96).to(BF16))
+        w2 = _c(weight.reshape(Cout, K).to(BF16))
         bf = _c(bias.float())
         gf = _c(gamma.float()) if gamma is not None else None
         bef = _c(beta.float()) if beta is not None else None
         want_masked = vmask is not None
         mt = _c(mask_token.reshape(-1).float()) if want_masked else None
         vm = _c(vmask.reshape(B, vmask.shape[-2], vmask.shape[-1]).long()) if want_masked else None
-        Tp, Hp, Wp = T // 2, H // 4, W // 4
+        Tp, Hp, Wp = patch_grid(T, H, W, patch, stride)
+        if want_masked and not fast and (Hp % vm.shape[1] or Wp % vm.shape[2]):
+            raise ValueError(f'patch embed: the mask grid {tuple(vm.shape[1:])} does not divide the token grid '
+                             f'{(Hp, Wp)} (the reference expands a mask cell over H\' // mh x W\' // mw tokens)')
         M = B * Tp * Hp * Wp
         dev = x.device
         need_grad = any(t is not None and t.requires_grad for t in (weight, bias, gamma, beta, mask_token))
@@ -1961,7 +1999,12 @@ class _PatchEmbed(torch.autograd.Function):
         mean = torch.empty(M, device=dev, dtype=torch.float32) if need_grad else None
         rstd = torch.empty(M, device=dev, dtype=torch.float32) if need_grad else None
         mh, mw = (vm.shape[1], vm.shape[2]) if want_masked else (1, 1)
-        if FP8:                                  # BASELINE config 5: the patch projection on the fp8 matrix instruction
+        if not fast:                             # any other geometry: the general kernel, in the 16-bit type (no fp8 form)
+            check(_lib.lib().clv_patch_embed_gen_fwd(_ptr(xc), _ptr(w2), _ptr(bf), _ptr(gf), _ptr(bef), _ptr(mt), _ptr(vm),
+                                                     _ptr(clean), _ptr(masked), _ptr(z), _ptr(mean), _ptr(rstd), B, T, H, W,
+                                                     Cout, mh, mw, *patch, *stride, float(eps), _stream()),
+                  'clv_patch_embed_gen_fwd')
+        elif FP8:                                # BASELINE config 5: the patch projection on the fp8 matrix instruction
             w8, wsc = quant_fp8_rows(w2)
             check(_lib.lib().clv_patch_embed_fwd_fp8(_ptr(xc), _ptr(w8), _ptr(wsc), _ptr(bf), _ptr(gf), _ptr(bef), _ptr(mt),
                                                      _ptr(vm), _ptr(clean), _ptr(masked), _ptr(z), _ptr(mean), _ptr(rstd),
@@ -1976,6 +2019,7 @@ class _PatchEmbed(torch.autograd.Function):
         ctx.meta = (B, T, H, W, Cout, want_clean, want_masked, weight.shape,
                     mask_token.shape if mask_token is not None else None)
         ctx.stacked = bool(stacked)
+        ctx.geom = (patch, stride)
         if stacked:
             return both, x.new_empty(0)
         outs = (clean if want_clean else x.new_empty(0), masked if want_masked else x.new_empty(0))
@@ -1985,7 +2029,10 @@ class _PatchEmbed(torch.autograd.Function):
     def backward(ctx, dclean, dmasked):
         xc, z, mean, rstd, gf, vm = ctx.saved_tensors
         B, T, H, W, Cout, want_clean, want_masked, wshape, mtshape = ctx.meta
-        Tp, Hp, Wp = T // 2, H // 4, W // 4
+        patch, stride = ctx.geom
+        fast = (patch, stride) == PE_FAST
+        K = 3 * patch[0] * patch[1] * patch[2]
+        Tp, Hp, Wp = patch_grid(T, H, W, patch, stride)
         M = B * Tp * Hp * Wp
         L = _lib.lib()
 
@@ -2011,8 +2058,12 @@ class _PatchEmbed(torch.autograd.Function):
             # dy = d_clean + d_masked (1 - w), d mask_token = sum d_masked w — one kernel (clv_patch_embed_blend_bwd)
             dyb = torch.empty(M, Cout, device=xc.device, dtype=BF16)
             dmt = msink.view(-1) if sink else torch.zeros(Cout, device=xc.device, dtype=torch.float32)
-            check(L.clv_patch_embed_blend_bwd(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, T, H, W, Cout,
-                                              vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd')
+            if fast:
+                check(L.clv_patch_embed_blend_bwd(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, T, H, W, Cout,
+                                                  vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd')
+            else:
+                check(L.clv_patch_embed_blend_bwd_gen(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, Tp, Hp, Wp, Cout,
+                                                      vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd_gen')
             dmt = None if sink else dmt.reshape(mtshape)
         if gf is not None:
             nblk = L.clv_layernorm_bwd_blocks(M, Cout)
@@ -2030,36 +2081,42 @@ class _PatchEmbed(torch.autograd.Function):
                 dg = db = None
         else:
             dz, dg, db = dyb, None, None
-        patches = torch.empty(M, 96, device=xc.device, dtype=BF16)
-        check(L.clv_im2col_patches(_ptr(xc), _ptr(patches), B, T, H, W, _stream()), 'clv_im2col_patches')
+        patches = torch.empty(M, K, device=xc.device, dtype=BF16)
+        if fast:
+            check(L.clv_im2col_patches(_ptr(xc), _ptr(patches), B, T, H, W, _stream()), 'clv_im2col_patches')
+        else:
+            check(L.clv_im2col_patches_gen(_ptr(xc), _ptr(patches), B, T, H, W, *patch, *stride, _stream()),
+                  'clv_im2col_patches_gen')
         if sink:
-            # the conv weight's sink goes in as its [Cout, 96] VIEW, not as the attribute object: a view carries neither
+            # the conv weight's sink goes in as its [Cout, K] VIEW, not as the attribute object: a view carries neither
             # first-touch state nor norm slots (_sinks), so this gradient always accumulates into a cleared slot and the
             # norm pass reads it.  Kept as it was: engine._setup_first_touch finds the slot non-finite in its poisoned
             # pass and goes on clearing it
-            linear_wgrad(dz, patches, True, wsink.view(Cout, 96), bsink.view(-1))
+            linear_wgrad(dz, patches, True, wsink.view(Cout, K), bsink.view(-1))
             _delivered(*ps)
-            return None, None, None, None, None, None, None, None, None, None
+            return (None,) * 12
         dw, dbias = linear_wgrad(dz, patches, True)
         dw = dw.reshape(wshape)
-        return None, dw, dbias, dg, db, dmt, None, None, None, None
+        return (None, dw, dbias, dg, db, dmt) + (None,) * 6
 
 
-def patch_embed(x, weight, bias, gamma, beta, mask_token=None, vmask=None, want_clean=True, eps=1e-5):
+def patch_embed(x, weight, bias, gamma, beta, mask_token=None, vmask=None, want_clean=True, eps=1e-5,
+                patch=PE_FAST[0], stride=PE_FAST[1]):
     """PatchEmbed3D + LN + mask-token blend. x fp32 [B,3,T,H,W] (already padded).
-    Returns (clean, masked) bf16 [B,T/2,H/4,W/4,C] channels-last (masked None without vmask)."""
+    Returns (clean, masked) bf16 [B,T',H',W',C] channels-last, (T',H',W') = patch_grid(...) (masked None without vmask).
+    patch = stride = (2,4,4): clv_patch_embed_fwd; any other geometry of the supported set: clv_patch_embed_gen_fwd."""
     if parity.enabled():
-        return parity.patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps)
-    clean, masked = _PatchEmbed.apply(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps)
+        return parity.patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, stride=stride)
+    clean, masked = _PatchEmbed.apply(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, False, patch, stride)
     return (clean if want_clean else None), (masked if vmask is not None else None)
 
 
-def patch_embed_stacked(x, weight, bias, gamma, beta, mask_token, vmask, eps=1e-5):
+def patch_embed_stacked(x, weight, bias, gamma, beta, mask_token, vmask, eps=1e-5, patch=PE_FAST[0], stride=PE_FAST[1]):
     """As patch_embed, but the clean and the masked tokens are written as the two halves of one bf16
-    [2B,T/2,H/4,W/4,C] tensor (clean first) — the layout the doubled Swin pass consumes, without a cat."""
+    [2B,T',H',W',C] tensor (clean first) — the layout the doubled Swin pass consumes, without a cat."""
     if parity.enabled():
-        return parity.patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, True, eps, stacked=True)
-    return _PatchEmbed.apply(x, weight, bias, gamma, beta, mask_token, vmask, True, eps, True)[0]
+        return parity.patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, True, eps, stacked=True, stride=stride)
+    return _PatchEmbed.apply(x, weight, bias, gamma, beta, mask_token, vmask, True, eps, True, patch, stride)[0]
 
 
 # --------------------------------------------------------------------------- MLM decoder (vocabulary projection)

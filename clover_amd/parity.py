@@ -174,28 +174,41 @@ def attention(qkv, table, rid, kmask, geom_kw):
     return rnd('act', o)
 
 
-def patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, stacked=False):
-    """PatchEmbed3D (swin_transformer_3d.py:665-688: Conv3d(kernel = stride = (2,4,4)) + LayerNorm) and the mask-token
-    blend (:226-229) in fp32: im2col view -> clv_sgemm_nt -> fp32 LayerNorm kernel -> blend.
-    Returns (clean, masked) fp32 channels-last [B,T/2,H/4,W/4,C] (or the stacked [2B,...] tensor)."""
+def patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps, stacked=False, stride=None):
+    """PatchEmbed3D (swin_transformer_3d.py:665-688: Conv3d(kernel = patch, stride = stride) + LayerNorm) and the mask-token
+    blend (:226-229) in fp32: im2col view -> clv_sgemm_nt -> fp32 LayerNorm kernel -> blend.  The patch is the weight's
+    own (pt, ph, pw); stride defaults to it.
+    Returns (clean, masked) fp32 channels-last [B,T',H',W',C] (or the stacked [2B,...] tensor)."""
     from . import ops
     B, Cin, T, H, W = x.shape
     Cout = weight.shape[0]
-    assert Cin == 3 and tuple(weight.shape[1:]) == (3, 2, 4, 4)
-    if T % 2 or H % 4 or W % 4:                            # right / bottom / back zero-pad to patch multiples (:679-680);
-        x = torch.nn.functional.pad(x, (0, -W % 4, 0, -H % 4, 0, -T % 2))      # PatchEmbed3D.pad has normally done it
+    pt, ph, pw = patch = tuple(int(v) for v in weight.shape[2:])
+    stride = patch if stride is None else tuple(int(v) for v in stride)
+    why = ops.patch_embed_refusal(patch, stride, Cin, Cout) if (patch, stride) != ops.PE_FAST else None
+    if why is not None:
+        raise NotImplementedError(f'patch embed: {why}')
+    assert Cin == 3 and weight.shape[1] == 3
+    K = 3 * pt * ph * pw
+    if T % pt or H % ph or W % pw:                         # right / bottom / back zero-pad to patch multiples (:679-680);
+        x = torch.nn.functional.pad(x, (0, -W % pw, 0, -H % ph, 0, -T % pt))   # PatchEmbed3D.pad has normally done it
         B, Cin, T, H, W = x.shape
-    Tp, Hp, Wp = T // 2, H // 4, W // 4
-    # patches [M, 96] in the weight's (c, dt, dh, dw) column order: a pure layout op
-    patches = (rnd('input', x.float()).reshape(B, 3, Tp, 2, Hp, 4, Wp, 4).permute(0, 2, 4, 6, 1, 3, 5, 7)
-               .reshape(B * Tp * Hp * Wp, 96))
-    z = _LinearP.apply(patches, weight.reshape(Cout, 96), bias)          # rounds the weight itself when asked to
+    Tp, Hp, Wp = ops.patch_grid(T, H, W, patch, stride)
+    # patches [M, K] in the weight's (c, dt, dh, dw) column order: a pure layout op
+    xr = rnd('input', x.float())
+    if stride == patch:
+        patches = xr.reshape(B, 3, Tp, pt, Hp, ph, Wp, pw).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B * Tp * Hp * Wp, K)
+    else:                                                  # overlapping patches: [B,3,T',H',W',pt,ph,pw] windows
+        win = xr.unfold(2, pt, stride[0]).unfold(3, ph, stride[1]).unfold(4, pw, stride[2])
+        patches = win.permute(0, 2, 3, 4, 1, 5, 6, 7).reshape(B * Tp * Hp * Wp, K)
+    z = _LinearP.apply(patches, weight.reshape(Cout, K), bias)          # rounds the weight itself when asked to
     if gamma is not None:
         z = ops.layer_norm(z, gamma, beta, eps)            # parity branch of ops.layer_norm: fp32 kernel
     clean = rnd('act', z).view(B, Tp, Hp, Wp, Cout)
     masked = None
     if vmask is not None:
         mh, mw = vmask.shape[-2], vmask.shape[-1]
+        if Hp % mh or Wp % mw:
+            raise ValueError(f'patch embed: the mask grid {(mh, mw)} does not divide the token grid {(Hp, Wp)}')
         w = vmask.reshape(B, 1, mh, 1, mw, 1).expand(B, Tp, mh, Hp // mh, mw, Wp // mw).reshape(B, Tp, Hp, Wp, 1)
         w = w.to(torch.float32)
         masked = rnd('act', z.view(B, Tp, Hp, Wp, Cout) * (1.0 - w) + mask_token.float().reshape(1, 1, 1, 1, Cout) * w)

@@ -120,7 +120,9 @@ class CloverPretrain(BaseRecognizer):
                     # the video-independent part of the fusion encoder's input (text + type embeddings, position table,
                     # key mask) here, behind the text encoder, not between the video encoder and the first fusion layer
                     mb = self.multimodal_backbone
-                    fusion_prep = mb.prepare(text_out, text_mask2, 2 * B, (imgs.shape[2] + 1) // 2, mb.spacial_tokens)
+                    pe = self.backbone.patch_embed       # the video encoder's temporal grid, from its patch and stride
+                    t_prep = ops.patch_grid(*imgs.shape[2:], pe.patch_size, pe.stride)[0]
+                    fusion_prep = mb.prepare(text_out, text_mask2, 2 * B, t_prep, mb.spacial_tokens)
 
         # ---- video encoder: clean (:91) + masked (:114) pass as one 2B-clip pass, channels-last [2B,T',h,w,Cf]
         vis_both = self.backbone.forward_both(imgs, v_token_mask, mid_cut=video_cut)

@@ -264,6 +264,39 @@ int clv_patch_embed_blend_bwd(const void* dclean, const void* dmasked, const int
 int clv_im2col_patches(const float* x, void* patches, int32_t B, int32_t T, int32_t H, int32_t W,
                        void* stream);
 
+/* PatchEmbed3D for any patch size (pt,ph,pw) and stride (st,sh,sw) of the supported set (new symbols in ABI 19; nothing
+ * existing changes).  clv_patch_embed_gen_supported is the single statement of that set (host only, no GPU needed):
+ * 0 when the geometry is covered, else the reason —
+ *   CLV_PE_GEN_BAD_PATCH   a patch extent < 1
+ *   CLV_PE_GEN_BAD_STRIDE  not 1 <= stride <= patch on every axis (no gaps between patches)
+ *   CLV_PE_GEN_BAD_VOLUME  pt*ph*pw % 8 != 0 (K = 3*pt*ph*pw must be a multiple of 8 for the weight-gradient kernels)
+ *   CLV_PE_GEN_BAD_K       K > 384
+ *   CLV_PE_GEN_BAD_WIDTH   C not in {48, 96, 128}
+ * The input has 3 channels.  Token grid: T' = (T - pt) / st + 1 (floor), likewise H' and W' (T >= pt, H >= ph, W >= pw;
+ * the caller pads to multiples of the PATCH as for clv_patch_embed_fwd); 3*T*H*W <= INT32_MAX.
+ * clv_patch_embed_gen_fwd: every argument and output as clv_patch_embed_fwd, with w bf16 [C][K] (= proj.weight.flatten(1),
+ * K = 3*pt*ph*pw, columns in (c, dt, dy, dx) order) and tokens [B][T'][H'][W'][C]; mh must divide H' and mw W' (else
+ * CLV_ERR_ARG).  At (2,4,4 | 2,4,4) the result is bit-identical to clv_patch_embed_fwd's.  It computes in the library's 16-bit
+ * element type; there is no fp8 form.
+ * clv_im2col_patches_gen: bf16 patches [M][K] in the same column order, the operand of the weight-gradient GEMM.
+ * clv_patch_embed_blend_bwd_gen: clv_patch_embed_blend_bwd with the token grid (Tp, Hp, Wp) passed in. */
+#define CLV_PE_GEN_BAD_PATCH 1
+#define CLV_PE_GEN_BAD_STRIDE 2
+#define CLV_PE_GEN_BAD_VOLUME 3
+#define CLV_PE_GEN_BAD_K 4
+#define CLV_PE_GEN_BAD_WIDTH 5
+int clv_patch_embed_gen_supported(int32_t pt, int32_t ph, int32_t pw, int32_t st, int32_t sh, int32_t sw, int32_t C);
+int clv_patch_embed_gen_fwd(const float* x, const void* w, const float* bias, const float* gamma, const float* beta,
+                            const float* mask_token, const int64_t* vmask, void* out_clean, void* out_masked,
+                            void* z_out, float* mean, float* rstd, int32_t B, int32_t T, int32_t H, int32_t W,
+                            int32_t C, int32_t mh, int32_t mw, int32_t pt, int32_t ph, int32_t pw, int32_t st,
+                            int32_t sh, int32_t sw, float eps, void* stream);
+int clv_im2col_patches_gen(const float* x, void* patches, int32_t B, int32_t T, int32_t H, int32_t W, int32_t pt,
+                           int32_t ph, int32_t pw, int32_t st, int32_t sh, int32_t sw, void* stream);
+int clv_patch_embed_blend_bwd_gen(const void* dclean, const void* dmasked, const int64_t* vmask, void* dy,
+                                  float* dmask_token, int32_t B, int32_t Tp, int32_t Hp, int32_t Wp, int32_t C,
+                                  int32_t mh, int32_t mw, void* stream);
+
 /* ------------------------------------------------------------------ Linear weight/bias gradient
  * dW[n][k] += sum_m dY[m][n] X[m][k], db[n] += sum_m dY[m][n] — the weight gradient of every
  * token-parallel nn.Linear on the path (qkv/proj/fc1/fc2/reduction, swin_transformer_3d.py:257-259,
