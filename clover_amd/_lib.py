@@ -35,7 +35,7 @@ def half_dtype():
     import torch
     return torch.float16 if HALF_F16 else torch.bfloat16
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 ERRORS = {-1: 'CLV_ERR_ARG (bad argument)', -2: 'CLV_ERR_UNSUPPORTED (shape not supported by the kernels)',
           -3: 'CLV_ERR_LAUNCH (HIP launch failed)'}
@@ -139,11 +139,9 @@ SIGNATURES = {
     'clv_patch_embed_fwd': (C.c_int, [_p] * 12 + [_i32] * 7 + [_f, _p]),
     'clv_patch_embed_fwd_fp8': (C.c_int, [_p] * 13 + [_i32] * 7 + [_f, _p]),
     'clv_patch_embed_blend_bwd': (C.c_int, [_p] * 5 + [_i32] * 7 + [_p]),
-    'clv_im2col_patches': (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p]),
+    'clv_im2col_patches': (C.c_int, [_p, _p] + [_i32] * 10 + [_p]),
     'clv_patch_embed_gen_supported': (C.c_int, [_i32] * 7),
     'clv_patch_embed_gen_fwd': (C.c_int, [_p] * 12 + [_i32] * 13 + [_f, _p]),
-    'clv_im2col_patches_gen': (C.c_int, [_p, _p] + [_i32] * 10 + [_p]),
-    'clv_patch_embed_blend_bwd_gen': (C.c_int, [_p] * 5 + [_i32] * 7 + [_p]),
     'clv_linear_wgrad_work_floats': (C.c_int64, [_i64, _i32, _i32]),
     'clv_linear_wgrad': (C.c_int, [_p] * 5 + [_i64, _i32, _i32, _i32, _i32, _p, _p, _i32, _p]),
     'clv_rowgemm_supported': (C.c_int, [_i32, _i32, _i32]),

@@ -341,12 +341,11 @@ class PatchEmbed3D(nn.Module):
         super().__init__()
         self.patch_size = tuple(int(v) for v in patch_size)
         self.stride = tuple(int(v) for v in stride)
-        # patch = stride = (2,4,4) (every Clover / VideoSwin config) runs clv_patch_embed_fwd; any other geometry the
-        # general kernel, whose supported set is stated once (clv_patch_embed_gen_supported) and refused here otherwise
-        if (self.patch_size, self.stride) != ops.PE_FAST or in_chans != 3:
-            why = ops.patch_embed_refusal(self.patch_size, self.stride, in_chans, embed_dim)
-            if why is not None:
-                raise NotImplementedError(f'PatchEmbed3D: {why}')
+        # patch = stride = (2,4,4) (every Clover / VideoSwin config) runs clv_patch_embed_fwd, any other geometry the
+        # general kernel; the supported set is stated once (clv_patch_embed_gen_supported) and refused here otherwise
+        why = ops.patch_embed_refusal(self.patch_size, self.stride, in_chans, embed_dim)
+        if why is not None:
+            raise NotImplementedError(f'PatchEmbed3D: {why}')
         self.in_chans = in_chans
         self.embed_dim = embed_dim
         self.proj = nn.Conv3d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.stride)

@@ -1959,19 +1959,15 @@ class _PatchEmbed(torch.autograd.Function):
         B, Cin, T, H, W = x.shape
         Cout = weight.shape[0]
         patch, stride = tuple(int(v) for v in patch), tuple(int(v) for v in stride)
-        fast = (patch, stride) == PE_FAST
         K = 3 * patch[0] * patch[1] * patch[2]
-        if fast:
-            assert Cin == 3 and tuple(weight.shape[1:]) == (3, 2, 4, 4), 'kernel covers patch (2,4,4), 3 input channels'
-        else:
-            why = patch_embed_refusal(patch, stride, Cin, Cout)
-            if why is not None:
-                raise NotImplementedError(f'patch embed: {why}')
-            if tuple(weight.shape[1:]) != (3,) + patch:
-                raise ValueError(f'patch embed: weight {tuple(weight.shape)} does not have the patch size {patch}')
-            if T % patch[0] or H % patch[1] or W % patch[2]:
-                raise ValueError(f'patch embed: clip {(T, H, W)} is not padded to multiples of the patch {patch} '
-                                 f'(PatchEmbed3D.pad)')
+        why = patch_embed_refusal(patch, stride, Cin, Cout)
+        if why is not None:
+            raise NotImplementedError(f'patch embed: {why}')
+        if tuple(weight.shape[1:]) != (3,) + patch:
+            raise ValueError(f'patch embed: weight {tuple(weight.shape)} does not have the patch size {patch}')
+        if T % patch[0] or H % patch[1] or W % patch[2]:
+            raise ValueError(f'patch embed: clip {(T, H, W)} is not padded to multiples of the patch {patch} '
+                             f'(PatchEmbed3D.pad)')
         xc = _c(x.float())
         w2 = _c(weight.reshape(Cout, K).to(BF16))
         bf = _c(bias.float())
@@ -1981,7 +1977,7 @@ class _PatchEmbed(torch.autograd.Function):
         mt = _c(mask_token.reshape(-1).float()) if want_masked else None
         vm = _c(vmask.reshape(B, vmask.shape[-2], vmask.shape[-1]).long()) if want_masked else None
         Tp, Hp, Wp = patch_grid(T, H, W, patch, stride)
-        if want_masked and not fast and (Hp % vm.shape[1] or Wp % vm.shape[2]):
+        if want_masked and (Hp % vm.shape[1] or Wp % vm.shape[2]):
             raise ValueError(f'patch embed: the mask grid {tuple(vm.shape[1:])} does not divide the token grid '
                              f'{(Hp, Wp)} (the reference expands a mask cell over H\' // mh x W\' // mw tokens)')
         M = B * Tp * Hp * Wp
@@ -1999,7 +1995,7 @@ class _PatchEmbed(torch.autograd.Function):
         mean = torch.empty(M, device=dev, dtype=torch.float32) if need_grad else None
         rstd = torch.empty(M, device=dev, dtype=torch.float32) if need_grad else None
         mh, mw = (vm.shape[1], vm.shape[2]) if want_masked else (1, 1)
-        if not fast:                             # any other geometry: the general kernel, in the 16-bit type (no fp8 form)
+        if (patch, stride) != PE_FAST:           # any other geometry: the general kernel, in the 16-bit type (no fp8 form)
             check(_lib.lib().clv_patch_embed_gen_fwd(_ptr(xc), _ptr(w2), _ptr(bf), _ptr(gf), _ptr(bef), _ptr(mt), _ptr(vm),
                                                      _ptr(clean), _ptr(masked), _ptr(z), _ptr(mean), _ptr(rstd), B, T, H, W,
                                                      Cout, mh, mw, *patch, *stride, float(eps), _stream()),
@@ -2030,7 +2026,6 @@ class _PatchEmbed(torch.autograd.Function):
         xc, z, mean, rstd, gf, vm = ctx.saved_tensors
         B, T, H, W, Cout, want_clean, want_masked, wshape, mtshape = ctx.meta
         patch, stride = ctx.geom
-        fast = (patch, stride) == PE_FAST
         K = 3 * patch[0] * patch[1] * patch[2]
         Tp, Hp, Wp = patch_grid(T, H, W, patch, stride)
         M = B * Tp * Hp * Wp
@@ -2058,12 +2053,8 @@ class _PatchEmbed(torch.autograd.Function):
             # dy = d_clean + d_masked (1 - w), d mask_token = sum d_masked w — one kernel (clv_patch_embed_blend_bwd)
             dyb = torch.empty(M, Cout, device=xc.device, dtype=BF16)
             dmt = msink.view(-1) if sink else torch.zeros(Cout, device=xc.device, dtype=torch.float32)
-            if fast:
-                check(L.clv_patch_embed_blend_bwd(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, T, H, W, Cout,
-                                                  vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd')
-            else:
-                check(L.clv_patch_embed_blend_bwd_gen(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, Tp, Hp, Wp, Cout,
-                                                      vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd_gen')
+            check(L.clv_patch_embed_blend_bwd(_ptr(dc), _ptr(dm), _ptr(vm), _ptr(dyb), _ptr(dmt), B, Tp, Hp, Wp, Cout,
+                                              vm.shape[1], vm.shape[2], _stream()), 'clv_patch_embed_blend_bwd')
             dmt = None if sink else dmt.reshape(mtshape)
         if gf is not None:
             nblk = L.clv_layernorm_bwd_blocks(M, Cout)
@@ -2082,11 +2073,7 @@ class _PatchEmbed(torch.autograd.Function):
         else:
             dz, dg, db = dyb, None, None
         patches = torch.empty(M, K, device=xc.device, dtype=BF16)
-        if fast:
-            check(L.clv_im2col_patches(_ptr(xc), _ptr(patches), B, T, H, W, _stream()), 'clv_im2col_patches')
-        else:
-            check(L.clv_im2col_patches_gen(_ptr(xc), _ptr(patches), B, T, H, W, *patch, *stride, _stream()),
-                  'clv_im2col_patches_gen')
+        check(L.clv_im2col_patches(_ptr(xc), _ptr(patches), B, T, H, W, *patch, *stride, _stream()), 'clv_im2col_patches')
         if sink:
             # the conv weight's sink goes in as its [Cout, K] VIEW, not as the attribute object: a view carries neither
             # first-touch state nor norm slots (_sinks), so this gradient always accumulates into a cleared slot and the

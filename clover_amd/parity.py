@@ -184,7 +184,7 @@ def patch_embed(x, weight, bias, gamma, beta, mask_token, vmask, want_clean, eps
     Cout = weight.shape[0]
     pt, ph, pw = patch = tuple(int(v) for v in weight.shape[2:])
     stride = patch if stride is None else tuple(int(v) for v in stride)
-    why = ops.patch_embed_refusal(patch, stride, Cin, Cout) if (patch, stride) != ops.PE_FAST else None
+    why = ops.patch_embed_refusal(patch, stride, Cin, Cout)
     if why is not None:
         raise NotImplementedError(f'patch embed: {why}')
     assert Cin == 3 and weight.shape[1] == 3

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CLV_ABI_VERSION 19
+#define CLV_ABI_VERSION 20
 #define CLV_ERR_ARG (-1)
 #define CLV_ERR_UNSUPPORTED (-2)
 #define CLV_ERR_LAUNCH (-3)
@@ -240,62 +240,50 @@ int clv_gelu_fwd(const void* x, void* y, int64_t n, int32_t is_f32, void* stream
 int clv_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, int32_t is_f32, void* stream);
 
 /* ------------------------------------------------------------------ patch embed
- * PatchEmbed3D.forward (swin_transformer_3d.py:671-688: conv3d k=s=(2,4,4) as a GEMM
- * over non-overlapping patches + bias + LayerNorm(C)) fused with the mask-token blend
- * of SwinTransformer3D.forward (:222-230).  x float [B][3][T][H][W] (T even, H,W
- * multiples of 4 — the caller pads, :675-680); w bf16 [C][96] (= proj.weight.flatten(1));
- * out_clean / out_masked bf16 [B][T/2][H/4][W/4][C] channels-last; either may be NULL.
- * vmask int64 [B][mh][mw] (the v_token_mask) and mask_token float [C] — required iff
- * out_masked != NULL.  gamma/beta float [C] or both NULL (patch_norm=False).
- * z_out (bf16 [M][C] pre-norm conv output), mean, rstd (float [M]): saved for backward,
- * may be NULL.  C in {48, 96, 128}. */
-int clv_patch_embed_fwd(const float* x, const void* w, const float* bias, const float* gamma,
-                        const float* beta, const float* mask_token, const int64_t* vmask,
-                        void* out_clean, void* out_masked, void* z_out, float* mean, float* rstd,
-                        int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t mh,
-                        int32_t mw, float eps, void* stream);
-/* Backward of the mask-token blend (:222-230): dy = d_clean + d_masked (1 - w) (bf16 [M][C]; either input may be NULL)
- * and dmask_token float [C] += sum over tokens of d_masked w (ACCUMULATED; caller zeroes), w from vmask as above. */
-int clv_patch_embed_blend_bwd(const void* dclean, const void* dmasked, const int64_t* vmask, void* dy,
-                              float* dmask_token, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C,
-                              int32_t mh, int32_t mw, void* stream);
-/* im2col of the clip into bf16 patches [M][96] (k = c*32 + dt*16 + dy*4 + dx): the operand
- * of the weight-gradient GEMM dW = dZ^T * patches (the conv3d weight grad of :681). */
-int clv_im2col_patches(const float* x, void* patches, int32_t B, int32_t T, int32_t H, int32_t W,
-                       void* stream);
-
-/* PatchEmbed3D for any patch size (pt,ph,pw) and stride (st,sh,sw) of the supported set (new symbols in ABI 19; nothing
- * existing changes).  clv_patch_embed_gen_supported is the single statement of that set (host only, no GPU needed):
+ * PatchEmbed3D.forward (swin_transformer_3d.py:671-688: conv3d as a GEMM over patches + bias + LayerNorm(C)) fused with
+ * the mask-token blend of SwinTransformer3D.forward (:222-230), for any patch size (pt,ph,pw) and stride (st,sh,sw) of
+ * the supported set.  clv_patch_embed_gen_supported is the single statement of that set (host only, no GPU needed):
  * 0 when the geometry is covered, else the reason —
  *   CLV_PE_GEN_BAD_PATCH   a patch extent < 1
  *   CLV_PE_GEN_BAD_STRIDE  not 1 <= stride <= patch on every axis (no gaps between patches)
  *   CLV_PE_GEN_BAD_VOLUME  pt*ph*pw % 8 != 0 (K = 3*pt*ph*pw must be a multiple of 8 for the weight-gradient kernels)
  *   CLV_PE_GEN_BAD_K       K > 384
  *   CLV_PE_GEN_BAD_WIDTH   C not in {48, 96, 128}
- * The input has 3 channels.  Token grid: T' = (T - pt) / st + 1 (floor), likewise H' and W' (T >= pt, H >= ph, W >= pw;
- * the caller pads to multiples of the PATCH as for clv_patch_embed_fwd); 3*T*H*W <= INT32_MAX.
- * clv_patch_embed_gen_fwd: every argument and output as clv_patch_embed_fwd, with w bf16 [C][K] (= proj.weight.flatten(1),
- * K = 3*pt*ph*pw, columns in (c, dt, dy, dx) order) and tokens [B][T'][H'][W'][C]; mh must divide H' and mw W' (else
- * CLV_ERR_ARG).  At (2,4,4 | 2,4,4) the result is bit-identical to clv_patch_embed_fwd's.  It computes in the library's 16-bit
- * element type; there is no fp8 form.
- * clv_im2col_patches_gen: bf16 patches [M][K] in the same column order, the operand of the weight-gradient GEMM.
- * clv_patch_embed_blend_bwd_gen: clv_patch_embed_blend_bwd with the token grid (Tp, Hp, Wp) passed in. */
+ * x float [B][3][T][H][W], padded by the caller to multiples of the PATCH (:675-680).  Token grid: T' = (T - pt) / st + 1
+ * (floor), likewise H' and W' (T >= pt, H >= ph, W >= pw); M = B*T'*H'*W'.
+ * clv_patch_embed_gen_fwd: w bf16 [C][K] (= proj.weight.flatten(1), K = 3*pt*ph*pw, columns in (c, dt, dy, dx) order);
+ * out_clean / out_masked bf16 [B][T'][H'][W'][C] channels-last; either may be NULL.  vmask int64 [B][mh][mw] (the
+ * v_token_mask) and mask_token float [C] — required iff out_masked != NULL; mh must divide H' and mw W' (else CLV_ERR_ARG).
+ * gamma/beta float [C] or both NULL (patch_norm=False).  z_out (bf16 [M][C] pre-norm conv output), mean, rstd (float [M]):
+ * saved for backward, may be NULL.  3*T*H*W <= INT32_MAX.  It computes in the library's 16-bit element type.
+ * clv_patch_embed_fwd: the same for patch = stride = (2,4,4) (T even, H, W multiples of 4; w [C][96]) with the weight held in
+ * registers; bit-identical to clv_patch_embed_gen_fwd at that geometry. */
 #define CLV_PE_GEN_BAD_PATCH 1
 #define CLV_PE_GEN_BAD_STRIDE 2
 #define CLV_PE_GEN_BAD_VOLUME 3
 #define CLV_PE_GEN_BAD_K 4
 #define CLV_PE_GEN_BAD_WIDTH 5
 int clv_patch_embed_gen_supported(int32_t pt, int32_t ph, int32_t pw, int32_t st, int32_t sh, int32_t sw, int32_t C);
+int clv_patch_embed_fwd(const float* x, const void* w, const float* bias, const float* gamma,
+                        const float* beta, const float* mask_token, const int64_t* vmask,
+                        void* out_clean, void* out_masked, void* z_out, float* mean, float* rstd,
+                        int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t mh,
+                        int32_t mw, float eps, void* stream);
 int clv_patch_embed_gen_fwd(const float* x, const void* w, const float* bias, const float* gamma, const float* beta,
                             const float* mask_token, const int64_t* vmask, void* out_clean, void* out_masked,
                             void* z_out, float* mean, float* rstd, int32_t B, int32_t T, int32_t H, int32_t W,
                             int32_t C, int32_t mh, int32_t mw, int32_t pt, int32_t ph, int32_t pw, int32_t st,
                             int32_t sh, int32_t sw, float eps, void* stream);
-int clv_im2col_patches_gen(const float* x, void* patches, int32_t B, int32_t T, int32_t H, int32_t W, int32_t pt,
-                           int32_t ph, int32_t pw, int32_t st, int32_t sh, int32_t sw, void* stream);
-int clv_patch_embed_blend_bwd_gen(const void* dclean, const void* dmasked, const int64_t* vmask, void* dy,
-                                  float* dmask_token, int32_t B, int32_t Tp, int32_t Hp, int32_t Wp, int32_t C,
-                                  int32_t mh, int32_t mw, void* stream);
+/* Backward of the mask-token blend (:222-230) on the token grid [B][Tp][Hp][Wp]: dy = d_clean + d_masked (1 - w)
+ * (bf16 [M][C], 16-byte aligned; either input may be NULL) and dmask_token float [C] += sum over tokens of d_masked w
+ * (ACCUMULATED; caller zeroes), w from vmask as above. */
+int clv_patch_embed_blend_bwd(const void* dclean, const void* dmasked, const int64_t* vmask, void* dy,
+                              float* dmask_token, int32_t B, int32_t Tp, int32_t Hp, int32_t Wp, int32_t C,
+                              int32_t mh, int32_t mw, void* stream);
+/* im2col of the clip into bf16 patches [M][K] (16-byte aligned; columns in the weight's (c, dt, dy, dx) order): the operand
+ * of the weight-gradient GEMM dW = dZ^T * patches (the conv3d weight grad of :681). */
+int clv_im2col_patches(const float* x, void* patches, int32_t B, int32_t T, int32_t H, int32_t W, int32_t pt,
+                       int32_t ph, int32_t pw, int32_t st, int32_t sh, int32_t sw, void* stream);
 
 /* ------------------------------------------------------------------ Linear weight/bias gradient
  * dW[n][k] += sum_m dY[m][n] X[m][k], db[n] += sum_m dY[m][n] — the weight gradient of every

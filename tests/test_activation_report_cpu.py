@@ -18,7 +18,7 @@ CTYPES = {'const void*': ctypes.c_void_p, 'void*': ctypes.c_void_p, 'int32_t': c
 def test_symbols_binding_and_abi_version():
     from clover_amd import _lib, ops
     hdr = open(os.path.join(ROOT, 'include', 'clover_hip.h')).read()
-    assert _lib.ABI_VERSION == 19 and re.search(r'#define CLV_ABI_VERSION 19\b', hdr)
+    assert _lib.ABI_VERSION == 20 and re.search(r'#define CLV_ABI_VERSION 20\b', hdr)
     sigs = {}
     for name in ('clv_act_report', 'clv_act_report_latch'):
         m = re.search(r'\bint\s+%s\s*\(([^)]*)\)\s*;' % name, hdr)
@@ -33,7 +33,7 @@ def test_symbols_binding_and_abi_version():
     for fname in ('libclover_hip_f16.so', 'libclover_hip.so'):
         so = ctypes.CDLL(os.path.join(ROOT, 'clover_amd', fname))
         so.clv_abi_version.restype = ctypes.c_int
-        assert so.clv_abi_version() == 19, fname
+        assert so.clv_abi_version() == 20, fname
         scan, latch = so.clv_act_report, so.clv_act_report_latch          # AttributeError: the symbol is not exported
         scan.restype, scan.argtypes = sigs['clv_act_report']
         latch.restype, latch.argtypes = sigs['clv_act_report_latch']

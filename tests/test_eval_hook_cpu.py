@@ -165,11 +165,11 @@ def test_cli_flags_and_loader_export(monkeypatch):
 
 def test_retrieval_symbols_exported_by_both_builds():
     from clover_amd import _lib
-    assert _lib.ABI_VERSION == 19
+    assert _lib.ABI_VERSION == 20
     pkg = os.path.dirname(_lib.LIB_PATH)
     for fname in ('libclover_hip_f16.so', 'libclover_hip.so'):
         so = ctypes.CDLL(os.path.join(pkg, fname))
-        assert so.clv_abi_version() == 19, fname
+        assert so.clv_abi_version() == 20, fname
         for name in ('clv_retrieval_work_bytes', 'clv_retrieval_rank'):
             assert hasattr(so, name) and name in _lib.SIGNATURES, (fname, name)
         wb = so.clv_retrieval_work_bytes

@@ -16,17 +16,17 @@ def test_both_builds_export_the_f32_qa_entries(fname):
     so = ctypes.CDLL(os.path.join(ROOT, 'clover_amd', fname))
     for sym in F32_ENTRIES:
         assert hasattr(so, sym), (fname, sym)
-    assert so.clv_abi_version() == 19
+    assert so.clv_abi_version() == 20
 
 
 def test_lib_binds_the_f32_qa_entries_like_their_16_bit_counterparts():
     from clover_amd import _lib
-    assert _lib.ABI_VERSION == 19
+    assert _lib.ABI_VERSION == 20
     for sym, twin in F32_ENTRIES.items():
         assert _lib.SIGNATURES[sym] == _lib.SIGNATURES[twin], sym
         fn = getattr(_lib.lib(), sym)
         assert fn.restype is ctypes.c_int and list(fn.argtypes) == list(_lib.SIGNATURES[sym][1])
-    assert _lib.lib().clv_abi_version() == 19
+    assert _lib.lib().clv_abi_version() == 20
 
 
 def test_entry_selection_is_by_mode_and_dtype():

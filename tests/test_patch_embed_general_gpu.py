@@ -1,5 +1,5 @@
-"""clv_patch_embed_gen_fwd / clv_im2col_patches_gen / clv_patch_embed_blend_bwd_gen: bit-exact on integer data, and held
-to the derived budget of tests/PATCH_EMBED_ERROR_BUDGET.md on random data, against the fp64 reference of
+"""clv_patch_embed_gen_fwd / clv_patch_embed_fwd / clv_im2col_patches / clv_patch_embed_blend_bwd: bit-exact on integer data,
+and held to the derived budget of tests/PATCH_EMBED_ERROR_BUDGET.md on random data, against the fp64 reference of
 tests/patch_embed_ref.py.  `-m gpu` only."""
 import functools
 
@@ -139,7 +139,7 @@ def test_masked_only_and_no_norm_outputs(patch, stride):
 
 
 @pytest.mark.parametrize('C', COUTS)
-@pytest.mark.parametrize('patch,stride', pr.GEOMETRIES[:5])
+@pytest.mark.parametrize('patch,stride', pr.GEOMETRIES)
 def test_backward_exact_on_integers(patch, stride, C):
     """No LayerNorm (gamma = beta = None), so dz = d_clean + d_masked (1 - w) is an integer: dW, dbias and d mask_token
     are sums of small integers, below 2^24 in magnitude — exact in fp32 in any order."""
@@ -171,9 +171,39 @@ def test_im2col_gen_is_the_index_map():
         xs = xs.to(HALF).float()
         out = torch.empty(idx.shape, device=DEV, dtype=HALF)
         xd = xs.to(DEV)
-        rc = _lib.lib().clv_im2col_patches_gen(o._ptr(xd), o._ptr(out), B, T, H, W, *patch, *stride, o._stream())
+        rc = _lib.lib().clv_im2col_patches(o._ptr(xd), o._ptr(out), B, T, H, W, *patch, *stride, o._stream())
         assert rc == 0
         assert torch.equal(out.cpu().float(), xs.reshape(-1)[idx])
+
+
+@pytest.mark.parametrize('C', COUTS)
+def test_blend_backward_entry_exact_on_integers(C):
+    """clv_patch_embed_blend_bwd alone, with the asymmetric 7 x 7 mask.  A block pass covers 42 / 21 / 16 rows at
+    C = 48 / 96 / 128 (at 48 the 42 rows leave 4 of the 256 threads idle).  Token grid (2, 3, 14, 14): M = 1176 = 28 * 42 =
+    56 * 21 fills whole passes at 48 and 96 and leaves a tail at 128 (73.5 passes); token grid (2, 1, 7, 7): M = 98, a tail
+    at every width.  Integer gradients in [-3, 3]: dy (|dy| <= 6) and d mask_token (|sum| <= 3 M) are exact in any order."""
+    o, L = ops(), _lib.lib()
+    p = o._ptr
+    for B, Tp, Hp, Wp in ((2, 3, 14, 14), (2, 1, 7, 7)):
+        M = B * Tp * Hp * Wp
+        assert M in (1176, 98) and M % 16 and (M == 1176 or all(M % (256 // (c // 8)) for c in COUTS))
+        vm = asym_mask(B)
+        wgt = pr.token_weight(vm, Tp, Hp, Wp)[:, None]
+        g = torch.Generator().manual_seed(11 + C)
+        dc = torch.randint(-3, 4, (M, C), generator=g).double()
+        dm = torch.randint(-3, 4, (M, C), generator=g).double()
+        dcd, dmd, vmd = dc.to(DEV, HALF), dm.to(DEV, HALF), vm.to(DEV)
+        for clean in (dcd, None):
+            dy = torch.full((M, C), float('nan'), device=DEV, dtype=HALF)
+            dmt = torch.zeros(C, device=DEV)
+            rc = L.clv_patch_embed_blend_bwd(p(clean), p(dmd), p(vmd), p(dy), p(dmt), B, Tp, Hp, Wp, C, 7, 7, o._stream())
+            torch.cuda.synchronize()
+            assert rc == 0, rc
+            want = (dc if clean is not None else 0) + dm * (1 - wgt)           # patch_embed_ref.Ref.backward
+            assert torch.equal(dy.cpu().double(), want)
+            assert torch.equal(dmt.cpu().double(), (dm * wgt).sum(0))
+    rc = L.clv_patch_embed_blend_bwd(p(dcd), p(dmd), p(vmd), p(dy), p(dmt), 2, 1, 7, 12, C, 7, 7, o._stream())
+    assert rc == -1                                                            # 12 % 7 != 0: CLV_ERR_ARG
 
 
 # ----------------------------------------------------------------------------- random data: the derived budget
@@ -270,3 +300,12 @@ def test_unpadded_clip_and_wrong_weight_are_refused_with_the_reason():
         ops().patch_embed(torch.zeros(1, 3, 3, 28, 36, device=DEV), w, b, None, None, None, None, True, 1e-5, (2, 4, 4), (1, 4, 4))
     with pytest.raises(ValueError, match='patch size'):
         ops().patch_embed(torch.zeros(1, 3, 4, 28, 36, device=DEV), w, b, None, None, None, None, True, 1e-5, (1, 4, 4), (1, 4, 4))
+
+
+def test_fast_geometry_is_refused_with_the_same_reasons():
+    w, b = torch.zeros(48, 3, 2, 4, 4, device=DEV), torch.zeros(48, device=DEV)
+    with pytest.raises(ValueError, match='not padded'):
+        ops().patch_embed(torch.zeros(1, 3, 3, 28, 36, device=DEV), w, b, None, None, None, None, True, 1e-5, *FAST)
+    mt, vm = torch.zeros(1, 48, 1, 1, 1, device=DEV), torch.zeros(1, 7, 7, dtype=torch.long, device=DEV)
+    with pytest.raises(ValueError, match='does not divide the token grid'):            # tokens 7 x 9; 9 % 7 != 0
+        ops().patch_embed(torch.zeros(1, 3, 2, 28, 36, device=DEV), w, b, None, None, mt, vm, True, 1e-5, *FAST)

@@ -97,7 +97,7 @@ def test_module_refuses_at_construction_with_the_reason():
     from clover_amd.backbones.swin_transformer_3d import PatchEmbed3D, SwinTransformer3D
     for kw, word in [(dict(patch_size=(2, 4, 4), stride=(4, 4, 4)), 'stride'), (dict(patch_size=(1, 2, 2), stride=(1, 2, 2)), 'multiple of 8'),
                      (dict(in_chans=1), 'in_chans'), (dict(patch_size=(4, 8, 8), stride=(4, 8, 8)), 'exceeds 384'),
-                     (dict(patch_size=(1, 4, 4), stride=(1, 4, 4), embed_dim=192), 'embed_dim')]:
+                     (dict(patch_size=(1, 4, 4), stride=(1, 4, 4), embed_dim=192), 'embed_dim'), (dict(embed_dim=192), 'embed_dim')]:
         with pytest.raises(NotImplementedError, match=word):
             PatchEmbed3D(**kw)
     with pytest.raises(NotImplementedError, match='stride'):

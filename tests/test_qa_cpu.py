@@ -168,7 +168,7 @@ def test_qa_abi_entries_are_exported_by_both_builds():
         for sym in ('clv_qa_answer_rows', 'clv_qa_head_fwd', 'clv_qa_mc_ce_fwd', 'clv_qa_head_bwd',
                     'clv_attn_probs_mean', 'clv_qa_head_supported'):
             getattr(so, sym)
-        assert so.clv_abi_version() == _lib.ABI_VERSION == 19
+        assert so.clv_abi_version() == _lib.ABI_VERSION == 20
         f = so.clv_qa_head_supported
         f.argtypes = [ctypes.c_int32] * 3
         assert f(768, 384, 1540) == 1 and f(128, 64, 37) == 1 and f(768, 256, 1) == 1

@@ -18,11 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_group_symbols_exported_by_both_builds():
     from clover_amd import _lib
-    assert _lib.ABI_VERSION == 19
+    assert _lib.ABI_VERSION == 20
     pkg = os.path.dirname(_lib.LIB_PATH)
     for fname in ('libclover_hip_f16.so', 'libclover_hip.so'):
         so = ctypes.CDLL(os.path.join(pkg, fname))
-        assert so.clv_abi_version() == 19, fname
+        assert so.clv_abi_version() == 20, fname
         for name in ('clv_retrieval_group_work_bytes', 'clv_retrieval_group_best'):
             assert hasattr(so, name) and name in _lib.SIGNATURES, (fname, name)
         wb = so.clv_retrieval_work_bytes
