@@ -117,6 +117,9 @@ SIGNATURES = {
     'clv_attn_seq_work_bytes': (C.c_int64, [C.POINTER(ClvAttnGeom)]),
     'clv_attn_seq_max_keys': (C.c_int, []),
     'clv_attn_seq_parts': (C.c_int, [C.POINTER(ClvAttnGeom)]),
+    'clv_attn_part_tokens': (C.c_int, [C.POINTER(ClvAttnGeom)]),
+    'clv_attn_window_supported': (C.c_int, [_i32] * 7),
+    'clv_attn_window_max_tokens': (C.c_int, []),
     'clv_attn_bwd_work_bytes': (C.c_int64, [C.POINTER(ClvAttnGeom)]),
     'clv_attn_bwd_one_kernel': (C.c_int, [C.POINTER(ClvAttnGeom)]),
     'clv_attn_dbias_index_count': (C.c_int64, [C.POINTER(ClvAttnGeom)]),

@@ -153,10 +153,22 @@ class WindowAttention3D(nn.Module):
             lin.weight._clv_want_t = ops.wants_transposed(lin.out_features, lin.in_features)
         self.proj_drop = nn.Dropout(proj_drop)
         trunc_normal_(self.relative_position_bias_table, std=.02)
+        self._checked = set()
+
+    def check_window(self, ws):
+        """Refuse, by name, an effective window the attention kernels do not take — at the first geometry that has it,
+        before any kernel runs (the set: ops.window_attention_refusal)."""
+        ws = tuple(int(v) for v in ws)
+        if ws in self._checked:
+            return
+        why = ops.window_attention_refusal(ws, self.window_size, self.dim // self.num_heads)
+        if why is not None:
+            raise NotImplementedError(f'WindowAttention3D(window_size={tuple(self.window_size)}): {why}')
+        self._checked.add(ws)
 
     def forward(self, x, ws, ss, rid):
         """x bf16 [B,Dp,Hp,Wp,C] (already LN'd and padded) -> same shape."""
-        N = ws[0] * ws[1] * ws[2]
+        self.check_window(ws)
         qkv = self.qkv(x)
         o = ops.window_attention(qkv, self.relative_position_bias_table, rid if any(s > 0 for s in ss) else None,
                                  ws, ss, self.num_heads, table_window=self.window_size)
@@ -234,6 +246,7 @@ class SwinTransformerBlock3D(nn.Module):
         B, D, H, W, C = x.shape
         ws, ss, rid = window_geometry((D, H, W), self.window_size, self.shift_size, x.device)
         at = self.attn
+        at.check_window(ws)
         if branch is None:
             qkv, s0 = ops.ln_linear(x, None, self.norm1.weight, self.norm1.bias, at.qkv.weight, at.qkv.bias,
                                     self.norm1.eps, stream_out=True)

@@ -57,6 +57,14 @@ struct Geom {
     // dq per key part, dk / dv per query part) to the caller's scratch as [part][...]; a combine kernel merges the P
     // partial results (seq_combine_*).  The last part may be shorter; the pad keys of EVERY part's last tile(s) carry
     // -inf.  nparts = 1: everything below degenerates to the plain kernels.
+    // large windows (mode 1, 448 < N <= WIN_MAX_TOKENS = 1024 tokens) take the same part plan with parts of at most
+    // WIN_ONE_PART_TILES = 25 tiles (the table band shares the LDS with the staged operands).  On top of a sequence's parts
+    // the kernels then keep, for the STAGED range [s0, s0 + Ns), its tensor rows, table offsets (linb) and region ids in
+    // LDS, and evaluate the looped token's tensor row (tok_row), table offset (win_lin) and region id (global rid) per
+    // tile; "straddles shift regions" is decided over the whole window.  The dS scratch keeps its fragment order with
+    // ceil(N / 16) key tiles per query tile: part sp writes key tiles [sp * pt16 / 16, ...).  That code is compiled into
+    // instantiations of its own (template MODE = 2, `WP` in the kernels), so the kernels of every geometry that ran before
+    // stay what they were.
     int grp0;                            // first group of this launch (the table-gradient path runs the dQ kernel in chunks)
     int nparts, pt16;
     int lddq, lddk, lddv;                // row strides of the dq / dk / dv OUTPUTS (= ldq / ldk / ldv unless partial)
@@ -73,9 +81,9 @@ __device__ __forceinline__ int win_lin(const Geom& G, int n) {
 // Per-workgroup bias state in LDS (mode 1): the head's table and 4 * lin(n) per window token (byte offsets).
 template <int NK>
 __device__ __forceinline__ void load_bias_table(const Geom& G, const float* table, int h, float* tab_s, int* linb_s,
-                                                int tid, int nthreads, float mul = 1.f) {
+                                                int tid, int nthreads, float mul = 1.f, int s0 = 0) {
     for (int i = tid; i < G.tbn; i += nthreads) tab_s[i] = table[(int64_t)(G.tb0 + i) * G.g.nH + h] * mul;   // [tlen][nH] parameter layout
-    for (int n = tid; n < NK; n += nthreads) linb_s[n] = (n < G.g.N) ? 4 * win_lin(G, n) : 0;
+    for (int n = tid; n < NK; n += nthreads) linb_s[n] = (s0 + n < G.g.N) ? 4 * win_lin(G, s0 + n) : 0;
 }
 
 __device__ __forceinline__ int64_t tok_row(const Geom& G, int grp, int n) {
@@ -160,8 +168,31 @@ __device__ __forceinline__ void token_rows(const Geom& G, int grp, int* row_s, i
 }
 // tensor row of a LOOPED token (query in fwd / dQ, key in dK / dV): the LDS map covers the staged part only once a
 // sequence is split, and a sequence's map is one multiply-add anyway
+template <bool WP = false>
 __device__ __forceinline__ int64_t loop_row(const Geom& G, const int* row_s, int grp, int n) {
+    if constexpr (WP) return tok_row(G, grp, n);
     return G.nparts > 1 ? (int64_t)grp * G.g.N + n : (int64_t)row_s[n];
+}
+// 4 * lin(n) and the region id of a LOOPED window token: from the LDS maps of the one staged part, computed / read from
+// global memory once the window is split (WP)
+template <bool WP>
+__device__ __forceinline__ int loop_linb(const Geom& G, const int* linb_s, int n) {
+    if constexpr (WP) return 4 * win_lin(G, n);
+    return linb_s[n];
+}
+template <bool WP>
+__device__ __forceinline__ int loop_rid(const Geom& G, const int* rid_s, const int* rid, int wloc, int n) {
+    if constexpr (WP) return rid[wloc * G.g.N + n];
+    return rid_s[n];
+}
+// a window in parts: the staged part's region ids + "the window straddles shift regions" over ALL its tokens
+template <int NK>
+__device__ __forceinline__ int stage_rid_part(const Geom& G, const int* rid, int wloc, int s0, int* rid_s, int tid, int nthr) {
+    const int N = G.g.N;
+    int differs = 0;
+    for (int n = tid; n < NK; n += nthr) rid_s[n] = (s0 + n < N) ? rid[wloc * N + s0 + n] : 0;
+    for (int n = tid; n < N; n += nthr) differs |= rid[wloc * N + n] != rid[wloc * N];
+    return differs;
 }
 
 typedef short v4s_t __attribute__((ext_vector_type(4)));
@@ -184,6 +215,7 @@ constexpr float LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ float exp_sub(float x, float negL2) { return __builtin_amdgcn_exp2f(fmaf(x, LOG2E, negL2)); }
 
 // ------------------------------------------------------------------------- forward
+// MODE 2 (`WP` below): a window of more than 448 tokens, run in parts (see Geom) — G.g.mode is 1 for it all the same
 template <int HD, int NKT, bool DROP, int MODE>
 __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
@@ -191,6 +223,7 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
     const int* __restrict__ rid, const float* __restrict__ kmask, const unsigned long long* __restrict__ seedp,
     Geom G) {
     constexpr int NK = NKT * 16, KS = (HD + 31) / 32, LDR = HD + 8, NC = HD / 16;
+    constexpr bool WP = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
     bf16_t* Vs = Ks + NK * LDR;
@@ -206,7 +239,7 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
 
     // window mode keeps no additive key array (its only term is -inf on the pad keys of the last tile: computed): with
     // 13 key tiles the workgroup then needs < 40 KB of LDS and FOUR share a CU instead of three
-    int* row_s = reinterpret_cast<int*>(aux + (MODE == 1 ? 1 : 2) * NK);
+    int* row_s = reinterpret_cast<int*>(aux + (MODE != 0 ? 1 : 2) * NK);
     int* linb_s = row_s + NK;                                // mode 1 + bias: 4 * lin(n)
     float* tab_s = reinterpret_cast<float*>(linb_s + NK);    //                the head's bias table
     int* flag_s = reinterpret_cast<int*>(tab_s + G.tls);     // "window straddles shift regions"
@@ -224,7 +257,7 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
             const int qt = wave + WAVES * part + ti * WAVES * G.tsplit;
             const int nq = qt * 16 + (lane & 15);
             const bool qv = qt < nqt && nq < N;
-            load_frags<HD>(qpre[ti], q + loop_row(G, row_s, grp, qv ? nq : 0) * G.g.ldq + h * HD, qv, lane);
+            load_frags<HD>(qpre[ti], q + loop_row<WP>(G, row_s, grp, qv ? nq : 0) * G.g.ldq + h * HD, qv, lane);
         }
     }
     // K is staged as K * scale * log2(e) and every additive term (bias table, key mask, region mask) is kept in log2
@@ -232,19 +265,23 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
     // operation per score less than scale-and-add after the MFMA.
     stage<HD, NK, true>(row_s, k, G.g.ldk, h, Ns, Ks, tid, THREADS, G.g.scale * LOG2E);
     stage<HD, NK>(row_s, v, G.g.ldv, h, Ns, Vs, tid);
-    if (MODE == 1 && bias) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, THREADS, LOG2E);
+    if (MODE != 0 && bias) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, THREADS, LOG2E, WP ? s0 : 0);
     int* rid_s = reinterpret_cast<int*>(aux);
     // kadd[n]: additive key term — the key mask (mode 0) for real keys, -inf for the pad keys of the last tile.
     float* kadd = aux + NK;
     const int wloc = (G.g.mode == 1) ? grp % G.nW : 0;
     int differs = 0;
-    for (int n = tid; n < NK; n += THREADS) {
-        if (MODE == 1 && rid) {
-            const int rv = (n < N) ? rid[wloc * N + n] : 0;
-            rid_s[n] = rv;
-            if (n < N) differs |= rv != rid[wloc * N];
+    if constexpr (WP) {
+        if (rid) differs = stage_rid_part<NK>(G, rid, wloc, s0, rid_s, tid, THREADS);
+    } else {
+        for (int n = tid; n < NK; n += THREADS) {
+            if (MODE != 0 && rid) {
+                const int rv = (n < N) ? rid[wloc * N + n] : 0;
+                rid_s[n] = rv;
+                if (n < N) differs |= rv != rid[wloc * N];
+            }
+            if (MODE == 0) kadd[n] = (n < Ns) ? (kmask ? kmask[(int64_t)grp * N + s0 + n] * LOG2E : 0.f) : -INFINITY;
         }
-        if (MODE == 0) kadd[n] = (n < Ns) ? (kmask ? kmask[(int64_t)grp * N + s0 + n] * LOG2E : 0.f) : -INFINITY;
     }
     // a shifted block's windows that lie inside ONE region (all but the last row / column of windows: 49 of 64 at
     // 56 x 56) need no mask: 12 VALU operations per key tile and query less
@@ -262,7 +299,7 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
         if (qt >= nqt) break;
         const int nq = qt * 16 + lr;
         const bool qv = nq < N;
-        const int64_t qrow = loop_row(G, row_s, grp, qv ? nq : 0);
+        const int64_t qrow = loop_row<WP>(G, row_s, grp, qv ? nq : 0);
         Frag8 qf[KS];
         if (PRE > 1) {
 #pragma unroll
@@ -274,9 +311,9 @@ __global__ void __launch_bounds__(THREADS, (NKT <= 16 ? 3 : 1)) attn_fwd_kernel(
         constexpr int CH = NKT > 16 ? 14 : NKT;             // key tiles per softmax chunk
         float p[CH][4];
         // relative-position bias from the LDS table: byte offset = 4 * (lin(q) + tcst) - 4 * lin(key)
-        const bool tb = MODE == 1 && bias != nullptr;
-        const char* tp = reinterpret_cast<const char*>(tab_s) + (tb ? linb_s[qv ? nq : 0] + 4 * G.tcst : 0);
-        const int rq = (MODE == 1 && rid && qv) ? rid_s[nq] : 0;
+        const bool tb = MODE != 0 && bias != nullptr;
+        const char* tp = reinterpret_cast<const char*>(tab_s) + (tb ? loop_linb<WP>(G, linb_s, qv ? nq : 0) + 4 * G.tcst : 0);
+        const int rq = (MODE != 0 && rid && qv) ? loop_rid<WP>(G, rid_s, rid, wloc, nq) : 0;
         float4 bnext = make_float4(0.f, 0.f, 0.f, 0.f);
         if (tb) bnext = table_bias4(tp, linb_s + lg * 4);
         // Long windows / sequences (25 / 28 key tiles) walk their keys in TWO chunks of <= 14 tiles with a running row
@@ -418,6 +455,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
     bf16_t* __restrict__ dq, bf16_t* __restrict__ ds_out, float* __restrict__ dsum,
     const unsigned long long* __restrict__ seedp, Geom G) {
     constexpr int NK = NKT * 16, KS = (HD + 31) / 32, LDR = HD + 8, NC = HD / 16;
+    constexpr bool WP = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
     bf16_t* Vs = Ks + NK * LDR;
@@ -435,7 +473,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
     const int grp = gh / G.g.nH + G.grp0, h = gh % G.g.nH;    // grp0: this launch covers groups [grp0, grp0 + gridDim / ..)
     const int N = G.g.N;
     const int s0 = sp * G.pt16, Ns = min(N - s0, G.pt16);     // staged keys [s0, s0 + Ns)
-    const bool tb = MODE == 1 && bias != nullptr;
+    const bool tb = MODE != 0 && bias != nullptr;
     int* flag_s = reinterpret_cast<int*>(tab_s + G.tls);
     if (tid == 0) *flag_s = 0;
 
@@ -454,7 +492,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
             const int qt = wave + nwaves * part + ti * nwaves * G.tsplit;
             const int nq = qt * 16 + (lane & 15);
             const bool qv = qt < nqt && nq < N;
-            const int64_t qrow = loop_row(G, row_s, grp, qv ? nq : 0);
+            const int64_t qrow = loop_row<WP>(G, row_s, grp, qv ? nq : 0);
             load_frags<HD>(qpre[ti], q + qrow * G.g.ldq + h * HD, qv, lane);
             load_frags<HD>(dopre[ti], dout + qrow * G.g.ldo + h * HD, qv, lane);
             load_frags<HD>(opre[ti], o + qrow * G.g.ldo + h * HD, qv, lane);
@@ -464,16 +502,21 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
     // dQ = dS . K * scale then is (dS . K') / log2(e)
     stage<HD, NK, true>(row_s, k, G.g.ldk, h, Ns, Ks, tid, nthr, G.g.scale * LOG2E);
     stage<HD, NK>(row_s, v, G.g.ldv, h, Ns, Vs, tid, nthr);
-    if (tb) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, nthr, LOG2E);
+    if (tb) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, nthr, LOG2E, WP ? s0 : 0);
     const int wloc = (G.g.mode == 1) ? grp % G.nW : 0;
     int differs = 0;
-    for (int n = tid; n < NK; n += nthr) {
-        if (MODE == 1 && rid) {
-            const int rv = (n < N) ? rid[wloc * N + n] : 0;
-            rid_s[n] = rv;
-            if (n < N) differs |= rv != rid[wloc * N];
+    if constexpr (WP) {
+        if (rid) differs = stage_rid_part<NK>(G, rid, wloc, s0, rid_s, tid, nthr);
+        for (int n = tid; n < NK; n += nthr) kadd[n] = (n < Ns) ? 0.f : -INFINITY;
+    } else {
+        for (int n = tid; n < NK; n += nthr) {
+            if (MODE != 0 && rid) {
+                const int rv = (n < N) ? rid[wloc * N + n] : 0;
+                rid_s[n] = rv;
+                if (n < N) differs |= rv != rid[wloc * N];
+            }
+            kadd[n] = (n < Ns) ? ((MODE == 0 && kmask) ? kmask[(int64_t)grp * N + s0 + n] * LOG2E : 0.f) : -INFINITY;
         }
-        kadd[n] = (n < Ns) ? ((MODE == 0 && kmask) ? kmask[(int64_t)grp * N + s0 + n] * LOG2E : 0.f) : -INFINITY;
     }
     if (differs) *flag_s = 1;
     __syncthreads();
@@ -487,7 +530,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
         if (qt >= nqt) break;
         const int nq = qt * 16 + lr;
         const bool qv = nq < N;
-        const int64_t qrow = loop_row(G, row_s, grp, qv ? nq : 0);
+        const int64_t qrow = loop_row<WP>(G, row_s, grp, qv ? nq : 0);
         Frag8 qf[KS], dof[KS], of[KS];
         if (PREF) {
 #pragma unroll
@@ -507,12 +550,16 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
         const unsigned rowid = (unsigned)li;
         if (qv && lg == 0) dsum[li] = dsm;
         const float nL2 = qv ? -lse[li] * LOG2E : 0.f;
-        const char* tp = reinterpret_cast<const char*>(tab_s) + (tb ? linb_s[qv ? nq : 0] + 4 * G.tcst : 0);
-        const int rq = (MODE == 1 && rid && qv) ? rid_s[nq] : 0;
+        const char* tp = reinterpret_cast<const char*>(tab_s) + (tb ? loop_linb<WP>(G, linb_s, qv ? nq : 0) + 4 * G.tcst : 0);
+        const int rq = (MODE != 0 && rid && qv) ? loop_rid<WP>(G, rid_s, rid, wloc, nq) : 0;
         // dS scratch in MFMA-fragment order [group][head][q tile][key tile][lane][4]: every store instruction of a
-        // wave is one contiguous 512-B run (row-major rows would be 32-B pieces of 128-B lines)
+        // wave is one contiguous 512-B run (row-major rows would be 32-B pieces of 128-B lines).  A window in parts (WP): nqt
+        // key tiles per query tile, this part's are [s0 / 16, s0 / 16 + tlim) — the tiles its instantiation pads beyond
+        // them belong to the next part (or to nobody)
+        const int tlim = WP ? (Ns + 15) >> 4 : NKT;
         bf16_t* dsfrag = (tb && ds_out)
-            ? ds_out + ((((int64_t)(grp - G.grp0) * G.g.nH + h) * nqt + qt) * NKT * 64 + lane) * 4 : nullptr;
+            ? (WP ? ds_out + (((((int64_t)(grp - G.grp0) * G.g.nH + h) * nqt + qt) * nqt + (s0 >> 4)) * 64 + lane) * 4
+                  : ds_out + ((((int64_t)(grp - G.grp0) * G.g.nH + h) * nqt + qt) * NKT * 64 + lane) * 4) : nullptr;
 
         // long windows walk their key tiles in chunks of 14: the packed dS of a chunk feeds the dQ MFMAs right away, so
         // 7 instead of 13-14 fragment registers stay live (with the per-tile fragment loads: 165 -> <= 128 VGPRs)
@@ -565,7 +612,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT), (NKT > 16 ? 2 : ((NKT == 13 
                 }
                 dsf[tt >> 1].u[(tt & 1) * 2 + 0] = pack2bf(ds[0], ds[1]);
                 dsf[tt >> 1].u[(tt & 1) * 2 + 1] = pack2bf(ds[2], ds[3]);
-                if (dsfrag)
+                if (dsfrag && (!WP || t < tlim))
                     *reinterpret_cast<uint2*>(dsfrag + t * 256) =
                         make_uint2(dsf[tt >> 1].u[(tt & 1) * 2 + 0], dsf[tt >> 1].u[(tt & 1) * 2 + 1]);
             }
@@ -604,6 +651,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT)) attn_bwd_dkv_kernel(
     const float* __restrict__ bias, const int* __restrict__ rid, const float* __restrict__ kmask,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, const unsigned long long* __restrict__ seedp, Geom G) {
     constexpr int NK = NKT * 16, KS = (HD + 31) / 32, LDR = HD + 8, NC = HD / 16;
+    constexpr bool WP = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16_t* Qs = reinterpret_cast<bf16_t*>(smem);
     bf16_t* dOs = Qs + NK * LDR;
@@ -622,7 +670,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT)) attn_bwd_dkv_kernel(
     int* row_s = reinterpret_cast<int*>(aux + NK);
     int* linb_s = row_s + NK;
     float* tab_s = reinterpret_cast<float*>(linb_s + NK);
-    const bool tb = MODE == 1 && bias != nullptr;
+    const bool tb = MODE != 0 && bias != nullptr;
     int* flag_s = reinterpret_cast<int*>(tab_s + G.tls);
     if (tid == 0) *flag_s = 0;
     token_rows<NK>(G, grp, row_s, tid, nthr, s0);
@@ -636,7 +684,7 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT)) attn_bwd_dkv_kernel(
         const int kt = wave + nwaves * part + ti * nwaves * G.tsplit;
         const int nk = kt * 16 + (lane & 15);
         const bool kv = kt < nkt && nk < N;
-        const int64_t krow = loop_row(G, row_s, grp, kv ? nk : 0);
+        const int64_t krow = loop_row<WP>(G, row_s, grp, kv ? nk : 0);
         load_frags<HD>(kpre[ti], k + krow * G.g.ldk + h * HD, kv, lane);
         load_frags<HD>(vpre[ti], v + krow * G.g.ldv + h * HD, kv, lane);
     }
@@ -644,15 +692,18 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT)) attn_bwd_dkv_kernel(
     // dK = dS^T . Q * scale then is (dS^T . Q') / log2(e)
     stage<HD, NK, true>(row_s, q, G.g.ldq, h, Ns, Qs, tid, nthr, G.g.scale * LOG2E);
     stage<HD, NK>(row_s, dout, G.g.ldo, h, Ns, dOs, tid, nthr);
-    if (tb) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, nthr, LOG2E);
+    if (tb) load_bias_table<NK>(G, bias, h, tab_s, linb_s, tid, nthr, LOG2E, WP ? s0 : 0);
     int* rid_s = reinterpret_cast<int*>(aux);
     const int wloc = (G.g.mode == 1) ? grp % G.nW : 0;
     int differs = 0;
+    if constexpr (WP) {
+        if (rid) differs = stage_rid_part<NK>(G, rid, wloc, s0, rid_s, tid, nthr);
+    }
     for (int n = tid; n < NK; n += nthr) {
         const int64_t li = ((int64_t)grp * G.g.nH + h) * N + s0 + n;
         L_s[n] = (n < Ns) ? -lse[li] * LOG2E : -INFINITY;   // -L * log2e (exp_sub's form); pad queries: P = exp2(-inf) = 0
         D_s[n] = (n < Ns) ? dsum[li] : 0.f;
-        if (MODE == 1 && rid) {
+        if (!WP && MODE != 0 && rid) {
             const int rv = (n < N) ? rid[wloc * N + n] : 0;
             rid_s[n] = rv;
             if (n < N) differs |= rv != rid[wloc * N];
@@ -670,13 +721,13 @@ __global__ void __launch_bounds__(DKV_THREADS(NKT)) attn_bwd_dkv_kernel(
         if (kt >= nkt) break;
         const int nk = kt * 16 + lr;
         const bool kv = nk < N;
-        const int64_t krow = loop_row(G, row_s, grp, kv ? nk : 0);
+        const int64_t krow = loop_row<WP>(G, row_s, grp, kv ? nk : 0);
         Frag8 kf[KS], vf[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) { kf[s] = kpre[ti][s]; vf[s] = vpre[ti][s]; }
-        const int rk = (MODE == 1 && rid && kv) ? rid_s[nk] : 0;
+        const int rk = (MODE != 0 && rid && kv) ? loop_rid<WP>(G, rid_s, rid, wloc, nk) : 0;
         const float kmv = (MODE == 0 && kmask && kv) ? kmask[(int64_t)grp * N + nk] * LOG2E : 0.f;   // this lane's key
-        const int ko = tb ? linb_s[kv ? nk : 0] - 4 * G.tcst : 0;     // slot(q, key) = lin(q) - (lin(key) - tcst)
+        const int ko = tb ? loop_linb<WP>(G, linb_s, kv ? nk : 0) - 4 * G.tcst : 0;     // slot(q, key) = lin(q) - (lin(key) - tcst)
 
         f32x4_t dvacc[NC], dkacc[NC];
 #pragma unroll
@@ -1554,10 +1605,11 @@ __global__ void __launch_bounds__(256) seq_combine_fwd_kernel(const bf16_t* __re
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t tokens = (int64_t)G.g.groups * G.g.N;
     if (idx >= tokens * cpr) return;
-    const int64_t row = idx / cpr;
-    const int c = (int)(idx - row * cpr) * 8, h = c / HD;
-    const int64_t grp = row / G.g.N, n = row - grp * G.g.N;
+    const int64_t tok = idx / cpr;
+    const int c = (int)(idx - tok * cpr) * 8, h = c / HD;
+    const int64_t grp = tok / G.g.N, n = tok - grp * G.g.N;
     const int64_t li = (grp * G.g.nH + h) * G.g.N + n;
+    const int64_t row = tok_row(G, (int)grp, (int)n);        // a window's partial o sits at the token's natural-layout row
     // the parts' lse values (up to SEQ_MAX_PARTS of them) are read once per pass instead of kept in a private array
     const float* lp = lse_part + li;
     float m = -INFINITY;
@@ -1608,6 +1660,12 @@ __global__ void __launch_bounds__(256) seq_combine_bwd_kernel(const bf16_t* __re
 constexpr int SEQ_ONE_PART_TILES = 28;       // 448 keys: the largest instantiation (LDS)
 constexpr int SEQ_MAX_KEYS = 4096;           // the bound of clv_attn_probs_mean as well: the QA attention map covers the same range
 constexpr int SEQ_MAX_PARTS = (SEQ_MAX_KEYS / 16 + SEQ_ONE_PART_TILES - 1) / SEQ_ONE_PART_TILES;   // 10
+// Windows beyond 448 tokens: parts of at most 25 tiles (the tile counts 16 and 25 of the 256- / 392-token windows,
+// compiled once more with MODE = 2).  25, not 28: beside the staged operands the LDS holds the head's table band — 27.9 KB for a (16, 8, 8)
+// table — and at hd 64 the dK / dV kernel of 26 tiles then takes 416 * 72 * 2 * 2 + 5 * 416 * 4 + 27.9 KB = 156.0 KB of the
+// 160 KB; 28 tiles would take 166 KB.  1024 tokens is the bound of the fp32 parity kernel (F32_MAXT * 64) as well.
+constexpr int WIN_ONE_PART_TILES = 25;
+constexpr int WIN_MAX_TOKENS = 1024;
 bool make_geom(const ClvAttnGeom* g, Geom& G) {
     if (!g) return false;
     G.g = *g;
@@ -1635,8 +1693,10 @@ bool make_geom(const ClvAttnGeom* g, Geom& G) {
         // K / V (Q / dO) of one (sample, head) exceed the LDS: P parts of at most 28 tiles (beyond SEQ_MAX_KEYS the 16-bit
         // launchers find no instantiation and report CLV_ERR_UNSUPPORTED; the fp32 parity kernel stages nothing and takes
         // any length)
-        if (g->mode == 0 && tiles > SEQ_ONE_PART_TILES && g->N <= SEQ_MAX_KEYS) {
-            G.nparts = (tiles + SEQ_ONE_PART_TILES - 1) / SEQ_ONE_PART_TILES;
+        const bool win_parts = g->mode == 1 && tiles > SEQ_ONE_PART_TILES && g->N <= WIN_MAX_TOKENS;
+        if ((g->mode == 0 && tiles > SEQ_ONE_PART_TILES && g->N <= SEQ_MAX_KEYS) || win_parts) {
+            const int per = win_parts ? WIN_ONE_PART_TILES : SEQ_ONE_PART_TILES;
+            G.nparts = (tiles + per - 1) / per;
             G.pt16 = (tiles + G.nparts - 1) / G.nparts * 16;
             // P workgroups of a (group, head, part) set share the looped tiles: each takes at most nkt >= pt16 / 16 of
             // them, so P * roundup(nkt, waves) >= tiles (the launch checks)
@@ -1681,6 +1741,17 @@ bool make_geom(const ClvAttnGeom* g, Geom& G) {
 
 constexpr size_t MAX_LDS = 160 * 1024;
 constexpr int DBIAS_SPLITS = 32;      // group slices of the dS reduction (partial sums, no atomics)
+// the scratch of the parts' partial results: the head of ClvAttnGeom.work (all of it, for a sequence); bytes rounded so
+// that the partial sums of the table gradient, which a deferring caller keeps behind it, stay 256-byte aligned
+inline void* part_scratch(const Geom& G) { return G.g.work; }
+inline int64_t part_scratch_bytes(const Geom& G) {
+    if (G.nparts == 1) return 0;
+    // forward: partial o + lse per part; backward: partial dq / dk / dv per part (the larger of the two)
+    const int64_t tc = (int64_t)G.g.groups * G.g.N * G.g.nH * G.g.hd;
+    const int64_t fwd = G.nparts * (tc * 2 + G.lse_ps * 4), bwd = G.nparts * 3 * tc * 2;
+    const int64_t b = fwd > bwd ? fwd : bwd;
+    return G.g.mode == 1 ? (b + 255) / 256 * 256 : b;
+}
 
 // bytes of the bf16 dS scratch (16 x 16 fragments of every (group, head)), rounded so that the fp32 dense sums that
 // follow it in `work` stay 256-byte aligned
@@ -1699,6 +1770,9 @@ template <int HD, int NKT>
 size_t dq_lds(int tls) { return 2 * (size_t)(NKT * 16) * (HD + 8) * 2 + 4 * (size_t)NKT * 16 * 4 + (size_t)tls * 4 + 16; }
 template <int HD, int NKT>
 size_t dkv_lds(int tls) { return 2 * (size_t)(NKT * 16) * (HD + 8) * 2 + 5 * (size_t)NKT * 16 * 4 + (size_t)tls * 4 + 16; }
+
+// the staged tile counts a window in parts runs on (plan_nkt): parts of up to 16 tiles (29..32 in all) and of 17..25
+constexpr bool WIN_PART_NKT(int nkt) { return nkt == 16 || nkt == 25; }
 
 // Three compiled variants per (HD, NKT): window (bias/rid, no dropout), sequence, sequence + dropout.
 #define CLV_PICK_N(KERNEL, NT, ...)                                                                    \
@@ -1728,6 +1802,11 @@ void set_attrs() {
     CLV_ATTR((attn_bwd_dkv_kernel<HD, NKE, false, 0>));
     CLV_ATTR((attn_bwd_dkv_kernel<HD, NKE, true, 0>));
     if constexpr (HD == 32 && (NKT == 13 || NKT == 25)) CLV_ATTR((attn_bwd_one_kernel<HD, NKT>));
+    if constexpr (WIN_PART_NKT(NKT)) {
+        CLV_ATTR((attn_fwd_kernel<HD, NKT, false, 2>));
+        CLV_ATTR((attn_bwd_dq_kernel<HD, NKT, false, 2>));
+        CLV_ATTR((attn_bwd_dkv_kernel<HD, NKE, false, 2>));
+    }
 #undef CLV_ATTR
 }
 
@@ -1746,13 +1825,21 @@ int launch_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
         return clv_check_launch();
     }
     // several key parts: partial o (dense [tokens][C]) + lse per part into the scratch, then the merge
-    if (!G.g.work || (NKT + WAVES - 1) / WAVES * WAVES * G.tsplit < (G.g.N + 15) / 16) return CLV_ERR_UNSUPPORTED;
+    if (!part_scratch(G) || (NKT + WAVES - 1) / WAVES * WAVES * G.tsplit < (G.g.N + 15) / 16) return CLV_ERR_UNSUPPORTED;
     Geom P = G;
     P.g.ldo = G.g.nH * G.g.hd;
-    bf16_t* o_part = reinterpret_cast<bf16_t*>(G.g.work);
+    bf16_t* o_part = reinterpret_cast<bf16_t*>(part_scratch(G));
     float* lse_part = reinterpret_cast<float*>(o_part + G.nparts * G.o_ps);
-    CLV_PICK(attn_fwd_kernel, <<<dim3(nblk), dim3(THREADS), lds, st>>>((const bf16_t*)q, (const bf16_t*)k,
-             (const bf16_t*)v, o_part, lse_part, bias, rid, kmask, seed, P));
+    if (G.g.mode == 1) {
+        if constexpr (WIN_PART_NKT(NKT))
+            attn_fwd_kernel<HD, NKT, false, 2><<<dim3(nblk), dim3(THREADS), lds, st>>>((const bf16_t*)q, (const bf16_t*)k,
+                (const bf16_t*)v, o_part, lse_part, bias, rid, kmask, seed, P);
+        else
+            return CLV_ERR_UNSUPPORTED;
+    } else {
+        CLV_PICK(attn_fwd_kernel, <<<dim3(nblk), dim3(THREADS), lds, st>>>((const bf16_t*)q, (const bf16_t*)k,
+                 (const bf16_t*)v, o_part, lse_part, bias, rid, kmask, seed, P));
+    }
     int rc = clv_check_launch();
     if (rc) return rc;
     const int64_t items = (int64_t)G.g.groups * G.g.N * (G.g.nH * G.g.hd / 8);
@@ -1797,11 +1884,11 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* o, const
     bf16_t* dv_out = (bf16_t*)dv;
     if (G.nparts > 1) {                                      // partial dq / dk / dv: scratch [part][dq | dk | dv][tokens][C]
         const int looped = (G.g.N + 15) / 16;
-        if (!G.g.work || (NKT + DKV_THREADS(NKT) / 64 - 1) / (DKV_THREADS(NKT) / 64) * (DKV_THREADS(NKT) / 64) * G.tsplit < looped ||
+        if (!part_scratch(G) || (NKT + DKV_THREADS(NKT) / 64 - 1) / (DKV_THREADS(NKT) / 64) * (DKV_THREADS(NKT) / 64) * G.tsplit < looped ||
             (NKE + DKV_THREADS(NKE) / 64 - 1) / (DKV_THREADS(NKE) / 64) * (DKV_THREADS(NKE) / 64) * G.tsplit < looped)
             return CLV_ERR_UNSUPPORTED;
         const int64_t tc = (int64_t)G.g.groups * G.g.N * G.g.nH * G.g.hd;
-        dq_out = reinterpret_cast<bf16_t*>(G.g.work);
+        dq_out = reinterpret_cast<bf16_t*>(part_scratch(G));
         dk_out = dq_out + tc;
         dv_out = dq_out + 2 * tc;
     }
@@ -1813,12 +1900,18 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* o, const
                 (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse, bias, rid,
                 dq_out, dk_out, dv_out, (bf16_t*)(bias ? work : nullptr), dsum, Gx);
     };
-    const int64_t E = (int64_t)G.g.nH * ((G.g.N + 15) / 16) * NKT * 64;
+    // key tiles per query tile of the dS scratch and of everything the table gradient derives from it (ds_tiles below)
+    const int DST = G.nparts > 1 ? (G.g.N + 15) / 16 : NKT;
+    const int64_t E = (int64_t)G.g.nH * ((G.g.N + 15) / 16) * DST * 64;
     // (the partial sums live behind the scratch, or — so that a caller who gathers later can release the scratch — in the
     // geometry's own `work` buffer: clv_attn_dbias_partial_bytes)
+    // A window in parts needs G.g.work for the parts' results: its partial sums follow them there when the caller defers
+    // the gather (stage bit 8), and sit behind the dS scratch otherwise.
+    const bool wparts = G.g.mode == 1 && G.nparts > 1;
     float* partial = !bias ? nullptr
-                     : G.g.work ? reinterpret_cast<float*>(G.g.work)
-                                : reinterpret_cast<float*>(reinterpret_cast<char*>(work) + ds_scratch_bytes(G, NKT));
+                     : wparts && (stages & 8) ? reinterpret_cast<float*>(reinterpret_cast<char*>(G.g.work) + part_scratch_bytes(G))
+                     : G.g.work && !wparts ? reinterpret_cast<float*>(G.g.work)
+                                : reinterpret_cast<float*>(reinterpret_cast<char*>(work) + ds_scratch_bytes(G, DST));
     // >= 16 groups per slice: the fp32 partial tables cost 2 x 16 B per 4 scores and slice, i.e. as much as the
     // bf16 scratch itself once a slice covers only 4 groups
     const int splits = dbias_splits(G);
@@ -1854,9 +1947,18 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* o, const
         rc = clv_check_launch();
         if (rc) return rc;
     } else if (stages & 1) {
-        CLV_PICK(attn_bwd_dq_kernel, <<<dim3(nblk), dim3(DKV_THREADS(NKT)), lds_a, st>>>((const bf16_t*)q, (const bf16_t*)k,
-                 (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse, bias, rid, kmask, dq_out,
-                 (bf16_t*)(bias ? work : nullptr), dsum, seed, G));
+        if (wparts) {
+            if constexpr (WIN_PART_NKT(NKT))
+                attn_bwd_dq_kernel<HD, NKT, false, 2><<<dim3(nblk), dim3(DKV_THREADS(NKT)), lds_a, st>>>((const bf16_t*)q,
+                    (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse, bias, rid, kmask, dq_out,
+                    (bf16_t*)(bias ? work : nullptr), dsum, seed, G);
+            else
+                return CLV_ERR_UNSUPPORTED;
+        } else {
+            CLV_PICK(attn_bwd_dq_kernel, <<<dim3(nblk), dim3(DKV_THREADS(NKT)), lds_a, st>>>((const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse, bias, rid, kmask, dq_out,
+                     (bf16_t*)(bias ? work : nullptr), dsum, seed, G));
+        }
         rc = clv_check_launch();
         if (rc) return rc;
     }
@@ -1870,23 +1972,31 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* o, const
             // the caller gathers later (clv_attn_dbias_gather_batch): nothing more to launch here
         } else if (G.g.dbias_index) {
             hipLaunchKernelGGL(dbias_gather_tab_kernel, dim3((G.tbn * G.g.nH + 3) / 4), dim3(256), 0, st, partial, dbias,
-                               G.g.dbias_index, NKT, G, splits, E * 4, G.tb0, G.tbn);
+                               G.g.dbias_index, DST, G, splits, E * 4, G.tb0, G.tbn);
         }
         else
-            hipLaunchKernelGGL(dbias_gather_kernel, dim3((G.tlen * G.g.nH + 3) / 4), dim3(256), 0, st, partial, dbias, NKT, G,
+            hipLaunchKernelGGL(dbias_gather_kernel, dim3((G.tlen * G.g.nH + 3) / 4), dim3(256), 0, st, partial, dbias, DST, G,
                                splits, E * 4);
         rc = clv_check_launch();
         if (rc) return rc;
     }
     if ((stages & 4) && !one) {
-        CLV_PICK_N(attn_bwd_dkv_kernel, NKE, <<<dim3(nblk), dim3(DKV_THREADS(NKE)), lds_b, st>>>((const bf16_t*)q, (const bf16_t*)k,
-                 (const bf16_t*)v, (const bf16_t*)dout, lse, dsum, bias, rid, kmask, dk_out, dv_out, seed, G));
+        if (wparts) {
+            if constexpr (WIN_PART_NKT(NKT))
+                attn_bwd_dkv_kernel<HD, NKE, false, 2><<<dim3(nblk), dim3(DKV_THREADS(NKE)), lds_b, st>>>((const bf16_t*)q,
+                    (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse, dsum, bias, rid, kmask, dk_out, dv_out, seed, G);
+            else
+                return CLV_ERR_UNSUPPORTED;
+        } else {
+            CLV_PICK_N(attn_bwd_dkv_kernel, NKE, <<<dim3(nblk), dim3(DKV_THREADS(NKE)), lds_b, st>>>((const bf16_t*)q, (const bf16_t*)k,
+                       (const bf16_t*)v, (const bf16_t*)dout, lse, dsum, bias, rid, kmask, dk_out, dv_out, seed, G));
+        }
         rc = clv_check_launch();
         if (rc) return rc;
         if (G.nparts > 1) {
             const int64_t items = 3 * (int64_t)G.g.groups * G.g.N * (G.g.nH * G.g.hd / 8);
             hipLaunchKernelGGL(seq_combine_bwd_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,
-                               reinterpret_cast<const bf16_t*>(G.g.work), (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, G);
+                               reinterpret_cast<const bf16_t*>(part_scratch(G)), (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, G);
             rc = clv_check_launch();
         }
     }
@@ -1901,6 +2011,16 @@ int pick_nkt(int N) {
     for (int o : opts) if (o >= need) return o;
     return -1;
 }
+
+// the instantiation that stages one part (or everything): a window in parts has the two of WIN_PART_NKT to choose from
+int plan_nkt(const Geom& G) {
+    if (G.g.mode == 1 && G.nparts > 1) return G.pt16 <= 256 ? 16 : 25;
+    return pick_nkt(G.nparts > 1 ? G.pt16 : G.g.N);
+}
+
+// key tiles per query tile of the dS scratch, the partial sums and the gather's index table: the instantiation's count, or
+// the window's own tile count once it runs in parts (-1: no instantiation)
+int ds_tiles(const Geom& G) { return G.nparts > 1 ? (G.g.N + 15) / 16 : pick_nkt(G.g.N); }
 
 #define DISPATCH_NKT(HDV, FN, ...)                                   \
     switch (nkt) {                                                   \
@@ -1926,7 +2046,7 @@ extern "C" int clv_attn_fwd(const void* q, const void* k, const void* v, void* o
     const unsigned long long* sp = (const unsigned long long*)seed;
     if (bias && (G.g.mode != 1 || G.tlen == 0)) return CLV_ERR_ARG;
     if (rid && G.g.mode != 1) return CLV_ERR_ARG;
-    const int nkt = pick_nkt(G.nparts > 1 ? G.pt16 : G.g.N);
+    const int nkt = plan_nkt(G);
     hipStream_t st = (hipStream_t)stream;
     if (G.g.hd == 16) { DISPATCH_NKT(16, launch_fwd, q, k, v, o, lse, bias, rid, kmask, sp, G, st) }
     if (G.g.hd == 32) { DISPATCH_NKT(32, launch_fwd, q, k, v, o, lse, bias, rid, kmask, sp, G, st) }
@@ -1936,7 +2056,7 @@ extern "C" int clv_attn_fwd(const void* q, const void* k, const void* v, void* o
 extern "C" int64_t clv_attn_bwd_work_bytes(const ClvAttnGeom* geom) {
     Geom G;
     if (!make_geom(geom, G) || G.g.mode != 1 || G.tlen == 0) return 0;
-    const int nkt = pick_nkt(G.g.N);
+    const int nkt = ds_tiles(G);
     if (nkt < 0) return 0;
     return ds_scratch_bytes(G, nkt) + (int64_t)(DBIAS_SPLITS + 1) * G.g.nH * ((G.g.N + 15) / 16) * nkt * 256 * 4;   // + fp32 partials, dense
 }
@@ -1944,9 +2064,9 @@ extern "C" int64_t clv_attn_bwd_work_bytes(const ClvAttnGeom* geom) {
 extern "C" int64_t clv_attn_dbias_partial_bytes(const ClvAttnGeom* geom) {
     Geom G;
     if (!make_geom(geom, G) || G.g.mode != 1 || G.tlen == 0) return 0;
-    const int nkt = pick_nkt(G.g.N);
+    const int nkt = ds_tiles(G);
     if (nkt < 0) return 0;
-    return (int64_t)dbias_splits(G) * G.g.nH * ((G.g.N + 15) / 16) * nkt * 256 * 4;
+    return part_scratch_bytes(G) + (int64_t)dbias_splits(G) * G.g.nH * ((G.g.N + 15) / 16) * nkt * 256 * 4;
 }
 
 extern "C" int clv_attn_bwd_one_kernel(const ClvAttnGeom* geom) {
@@ -1958,31 +2078,67 @@ extern "C" int clv_attn_bwd_one_kernel(const ClvAttnGeom* geom) {
 
 extern "C" int64_t clv_attn_seq_work_bytes(const ClvAttnGeom* geom) {
     Geom G;
-    if (!make_geom(geom, G) || G.nparts == 1) return 0;
-    // forward: partial o + lse per part; backward: partial dq / dk / dv per part (the larger of the two)
-    const int64_t tc = (int64_t)G.g.groups * G.g.N * G.g.nH * G.g.hd;
-    const int64_t fwd = G.nparts * (tc * 2 + G.lse_ps * 4), bwd = G.nparts * 3 * tc * 2;
-    return fwd > bwd ? fwd : bwd;
+    if (!make_geom(geom, G)) return 0;
+    return part_scratch_bytes(G);
 }
 
 extern "C" int clv_attn_seq_max_keys(void) { return SEQ_MAX_KEYS; }
 
+// The largest LDS request of the three kernels of a window geometry with its table band staged (the launchers' own check,
+// fwd_lds / dq_lds / dkv_lds, by value instead of by instantiation): the dK / dV kernel's, at the next even tile count.
+static size_t window_lds_max(const Geom& G, int nkt) {
+    const size_t nke = (size_t)((nkt + 1) & ~1) * 16;
+    return 2 * nke * (G.g.hd + 8) * 2 + 5 * nke * 4 + (size_t)G.tls * 4 + 16;
+}
+
 extern "C" int clv_attn_seq_parts(const ClvAttnGeom* geom) {
     Geom G;
-    if (!make_geom(geom, G) || pick_nkt(G.nparts > 1 ? G.pt16 : G.g.N) < 0) return 0;
+    if (!make_geom(geom, G)) return 0;
+    const int nkt = plan_nkt(G);
+    if (nkt < 0 || (G.g.mode == 1 && window_lds_max(G, nkt) > MAX_LDS)) return 0;
     return G.nparts;
+}
+
+extern "C" int clv_attn_part_tokens(const ClvAttnGeom* geom) {
+    Geom G;
+    return clv_attn_seq_parts(geom) > 0 && make_geom(geom, G) ? G.pt16 : 0;
+}
+
+extern "C" int clv_attn_window_max_tokens(void) { return WIN_MAX_TOKENS; }
+
+extern "C" int clv_attn_window_supported(int32_t wd, int32_t wh, int32_t ww, int32_t bwd, int32_t bwh, int32_t bww, int32_t hd) {
+    if (wd <= 0 || wh <= 0 || ww <= 0 || bwd < 0 || bwh < 0 || bww < 0) return 1;
+    const bool table = bwd || bwh || bww;
+    if (table && (bwd <= 0 || bwh <= 0 || bww <= 0)) return 1;
+    if (hd != 16 && hd != 32 && hd != 64) return 2;
+    const int64_t n = (int64_t)wd * wh * ww;
+    if (n > WIN_MAX_TOKENS) return 3;
+    if (table && n > (int64_t)bwd * bwh * bww) return 4;
+    // one window of the geometry: the plan depends on (N, hd) and the table band only
+    ClvAttnGeom g = {};
+    g.mode = 1; g.groups = 1; g.N = (int)n; g.nH = 1; g.hd = hd;
+    g.D = g.wd = wd; g.H = g.wh = wh; g.W = g.ww = ww;
+    g.ldq = g.ldk = g.ldv = 3 * hd; g.ldo = hd;
+    g.bwd = bwd; g.bwh = bwh; g.bww = bww;
+    Geom G;
+    if (!make_geom(&g, G)) return 1;
+    const int nkt = plan_nkt(G);
+    if (nkt < 0) return 3;
+    return window_lds_max(G, nkt) > MAX_LDS ? 5 : 0;
 }
 
 extern "C" int64_t clv_attn_dbias_index_count(const ClvAttnGeom* geom) {
     Geom G;
     if (!make_geom(geom, G) || G.g.mode != 1 || G.tlen == 0) return 0;
-    return (int64_t)G.tlen * pick_nkt(G.g.N) * 16;
+    const int nkt = ds_tiles(G);
+    return nkt < 0 ? 0 : (int64_t)G.tlen * nkt * 16;
 }
 
 extern "C" int clv_attn_dbias_index(const ClvAttnGeom* geom, int32_t* out, void* stream) {
     Geom G;
     if (!out || !make_geom(geom, G) || G.g.mode != 1 || G.tlen == 0) return CLV_ERR_ARG;
-    const int nkt = pick_nkt(G.g.N);
+    const int nkt = ds_tiles(G);
+    if (nkt < 0) return CLV_ERR_UNSUPPORTED;
     const int64_t n = (int64_t)G.tlen * nkt * 16;
     hipLaunchKernelGGL(dbias_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, nkt, G);
     return clv_check_launch();
@@ -1999,7 +2155,7 @@ extern "C" int clv_attn_bwd(const void* q, const void* k, const void* v, const v
     if (bias && (G.g.mode != 1 || G.tlen == 0 || !dbias || !work)) return CLV_ERR_ARG;
     if (rid && G.g.mode != 1) return CLV_ERR_ARG;
     if (G.drop_thresh && !seed) return CLV_ERR_ARG;
-    const int nkt = pick_nkt(G.nparts > 1 ? G.pt16 : G.g.N);
+    const int nkt = plan_nkt(G);
     hipStream_t st = (hipStream_t)stream;
     if (G.g.hd == 16) { DISPATCH_NKT(16, launch_bwd, q, k, v, o, dout, lse, bias, rid, kmask, dq, dk, dv, dbias, dsum, work, sp, stages, G, st) }
     if (G.g.hd == 32) { DISPATCH_NKT(32, launch_bwd, q, k, v, o, dout, lse, bias, rid, kmask, dq, dk, dv, dbias, dsum, work, sp, stages, G, st) }
@@ -2011,10 +2167,12 @@ extern "C" int clv_attn_dbias_gather_entry(const ClvAttnGeom* geom, void* work, 
     Geom G;
     if (!geom || !work || !dbias || !out || !make_geom(geom, G) || G.g.mode != 1 || G.tlen == 0 || !G.g.dbias_index)
         return CLV_ERR_ARG;
-    const int nkt = pick_nkt(G.g.N);
+    const int nkt = ds_tiles(G);
     if (nkt < 0) return CLV_ERR_UNSUPPORTED;
     const int64_t E = (int64_t)G.g.nH * ((G.g.N + 15) / 16) * nkt * 64;
-    out->partial = G.g.work ? reinterpret_cast<char*>(G.g.work) : reinterpret_cast<char*>(work) + ds_scratch_bytes(G, nkt);
+    if (G.nparts > 1 && !G.g.work) return CLV_ERR_ARG;
+    out->partial = G.g.work ? reinterpret_cast<char*>(G.g.work) + part_scratch_bytes(G)
+                            : reinterpret_cast<char*>(work) + ds_scratch_bytes(G, nkt);
     out->dtable = dbias;
     out->index = G.g.dbias_index;
     out->split_stride = E * 4;

@@ -4,7 +4,7 @@ These own every tensor, pass ``data_ptr()`` + the current HIP stream through cty
 are what the registered nn.Modules call.  No CPU path exists: a non-HIP tensor raises.
 """
 import ctypes as C
-
+import functools
 import os
 from typing import Any, NamedTuple, Optional
 
@@ -166,20 +166,26 @@ def _dbias_index(g, device):
 def _kname(kernel, g):
     """Device-kernel name as rocprofv3 prints it: template <HD, NKT, DROP, MODE> (attention.hip CLV_PICK)."""
     need = (g.N + 15) // 16
-    if g.mode == 0 and need > 28:             # a long sequence runs as P parts of staged tokens (attention.hip make_geom):
-        parts = (need + 27) // 28             # the instantiation is chosen from the PART's tiles, not from N
+    mode = g.mode
+    if need > 28 and (g.mode == 0 or g.N <= WINDOW_MAX_TOKENS):
+        # a long sequence, or a window beyond 448 tokens, runs as P parts of staged tokens (attention.hip make_geom): the
+        # instantiation is chosen from the PART's tiles, not from N; a window's parts hold at most 25 tiles (the table band
+        # shares the LDS) and run the instantiations of template MODE 2
+        per = 28 if g.mode == 0 else 25
+        parts = (need + per - 1) // per
         need = (need + parts - 1) // parts
-    nkt = next((o for o in (2, 8, 13, 14, 15, 16, 25, 28) if o >= need), need)       # > 28: the C call reports UNSUPPORTED
+        mode = 0 if g.mode == 0 else 2
+    nkt = next((o for o in ((16, 25) if mode == 2 else (2, 8, 13, 14, 15, 16, 25, 28)) if o >= need), need)   # > 28: UNSUPPORTED
     drop = 'true' if (g.dropout_p > 0 and g.mode == 0) else 'false'
     if kernel == 'attn_bwd_dkv_kernel':
         nkt = (nkt + 1) & ~1                  # the dK / dV kernel runs the next even tile count (attention.hip launch_bwd)
-    return f'{kernel}<{g.hd}, {nkt}, {drop}, {g.mode}>'
+    return f'{kernel}<{g.hd}, {nkt}, {drop}, {mode}>'
 
 
 def _attn_work(g, backward):
     """Algorithmic work of one attention call: 2 flops/MAC over the
     N x N x hd products (2 matmuls forward, 5 backward); bytes = q,k,v read + o written
-    (forward) or q,k,v,o,do read + dq,dk,dv written (backward), bf16.  A sequence run as P parts does the same N x N
+    (forward) or q,k,v,o,do read + dq,dk,dv written (backward), bf16.  A sequence or a window run as P parts does the same N x N
     products (every part set walks all looped tiles against its own part of the staged ones); the P-fold re-staging and
     the partial results in the scratch are the implementation's traffic, not counted here."""
     per = g.groups * g.nH * g.N * g.N * g.hd
@@ -1776,6 +1782,32 @@ class _Attention(torch.autograd.Function):
         return dqkv, dtab, None, None, None, None
 
 
+# the largest window of the 16-bit kernels and of the fp32 parity kernel alike (attention.hip WIN_MAX_TOKENS, F32_MAXT * 64)
+WINDOW_MAX_TOKENS = _lib.lib().clv_attn_window_max_tokens()
+_WIN_REASONS = {1: 'a window extent below 1', 2: 'head dim must be 16, 32 or 64',
+                3: 'more than %d tokens per window' % WINDOW_MAX_TOKENS,
+                4: 'the window has more tokens than the window its relative-position table was built for',
+                5: 'the staged part of the window and its table band exceed the 160 KB of LDS'}
+
+
+@functools.lru_cache(maxsize=None)
+def _window_refusal(window, table_window, hd):
+    rc = _lib.lib().clv_attn_window_supported(*window, *table_window, hd)
+    if rc == 0:
+        return None
+    n = window[0] * window[1] * window[2]
+    return (f'window {window} = {n} tokens (table window {table_window}, head dim {hd}): {_WIN_REASONS.get(rc, rc)}; '
+            f'the attention kernels take windows of up to {WINDOW_MAX_TOKENS} tokens')
+
+
+def window_attention_refusal(window, table_window, hd):
+    """None when the HIP window-attention kernels (16-bit and parity alike) cover the window, else the reason as text.
+    window: the effective window of the call; table_window: the window the relative-position table was built for (None:
+    no table).  The set itself is stated once, in clv_attn_window_supported (host only: no GPU needed)."""
+    tw = tuple(int(v) for v in table_window) if table_window is not None else (0, 0, 0)
+    return _window_refusal(tuple(int(v) for v in window), tw, int(hd))
+
+
 def window_attention(qkv, table, rid, window, shift, num_heads, table_window=None):
     """3-D shifted-window MHA on the natural token layout.
 
@@ -1791,6 +1823,9 @@ def window_attention(qkv, table, rid, window, shift, num_heads, table_window=Non
     N = window[0] * window[1] * window[2]
     nW = (D // window[0]) * (H // window[1]) * (W // window[2])
     tw = tuple(table_window or window) if table is not None else (0, 0, 0)
+    why = window_attention_refusal(window, tw if table is not None else None, hd)
+    if why is not None:
+        raise NotImplementedError(f'window attention: {why}')
     kw = dict(mode=1, groups=B * nW, N=N, nH=num_heads, hd=hd, D=D, H=H, W=W, wd=window[0], wh=window[1],
               ww=window[2], sd=shift[0], sh=shift[1], sw=shift[2], bwd=tw[0], bwh=tw[1], bww=tw[2],
               scale=float(hd) ** -0.5)

@@ -84,7 +84,16 @@ typedef struct ClvAttnGeom {
                                    aligned memory that receives the slices' fp32 partial sums of the table gradient INSTEAD
                                    of the tail of clv_attn_bwd's `work` — a caller that gathers later (stage bit 8 +
                                    clv_attn_dbias_gather_batch) keeps only this and releases the dS scratch (GBs at 32
-                                   frames).  Not read otherwise. */
+                                   frames).  Not read otherwise.
+                                   mode 1 with 448 < N <= clv_attn_window_max_tokens() = 1024 (the (16, 7, 7) windows of the
+                                   32-frame checkpoints, 784 tokens; 12 x 12 spatial windows), forward and backward, required:
+                                   clv_attn_seq_work_bytes() of scratch for the same part plan — P = clv_attn_seq_parts() =
+                                   ceil(ceil(N / 16) / 25) parts of clv_attn_part_tokens() staged tokens, beside which the
+                                   head's table band stays in LDS.  A caller that gathers later (stage bit 8) passes
+                                   clv_attn_dbias_partial_bytes() instead, which for such a window is that scratch rounded up
+                                   to 256 bytes FOLLOWED by the partial sums; without bit 8 the partial sums of such a window
+                                   go to the tail of clv_attn_bwd's `work`.  Between the stages of a backward run stage by
+                                   stage (1, 2, 4) the buffer must stay untouched. */
 } ClvAttnGeom;
 
 /* lse: float [groups][nH][N].  bias: the module's relative_position_bias_table, float [rows][nH], or NULL.  rid: int32 [nW][N] region
@@ -96,6 +105,15 @@ int clv_attn_seq_max_keys(void);
 /* The number of parts the staged tokens of this geometry are split in: 1 = not split (no scratch needed), 0 = the 16-bit
  * kernels do not take the geometry (clv_attn_fwd / clv_attn_bwd report an error). */
 int clv_attn_seq_parts(const ClvAttnGeom* geom);
+/* Host-only plan of a geometry run in parts (both modes): the tokens each part stages, a multiple of 16 — the last
+ * part may stage fewer; N rounded up to 16 for a geometry of one part; 0 where clv_attn_seq_parts() is 0. */
+int clv_attn_part_tokens(const ClvAttnGeom* geom);
+/* Which windows the 16-bit kernels take (host only, no GPU needed — the single statement of the set):
+ * window (wd, wh, ww) under a table built for (bwd, bwh, bww) (0, 0, 0 = no table), head dim hd.  0 = supported, else
+ * 1 bad extents, 2 head dim not 16 / 32 / 64, 3 more than clv_attn_window_max_tokens() tokens, 4 the window has more tokens
+ * than the table's window, 5 staged part + table band exceed the 160 KB of LDS. */
+int clv_attn_window_supported(int32_t wd, int32_t wh, int32_t ww, int32_t bwd, int32_t bwh, int32_t bww, int32_t hd);
+int clv_attn_window_max_tokens(void);
 int clv_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
                  const float* bias, const int32_t* rid, const float* kmask, const void* seed,
                  const ClvAttnGeom* geom_host, void* stream);
