@@ -231,6 +231,10 @@ SIGNATURES = {
     'clv_retrieval_rank': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _i32, _p]),
     'clv_retrieval_group_work_bytes': (C.c_int64, [_i64, _i64, _i32]),
     'clv_retrieval_group_best': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _f, _p]),
+    'clv_retrieval_col_stats_work_bytes': (C.c_int64, [_i64, _i64, _i32]),
+    'clv_retrieval_col_stats': (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _i64, _f, _p, _p, _p, _p]),
+    'clv_retrieval_rank_prior_work_bytes': (C.c_int64, [_i64, _i64, _i32, _i32]),
+    'clv_retrieval_rank_prior': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _i32, _p, _p, _f, _p]),
 }
 
 _lib = None

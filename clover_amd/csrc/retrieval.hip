@@ -31,6 +31,18 @@
 // one thread per query keeps the first maximum of its range.  retrieval_best_merge_kernel joins the chunks; the rank of
 // that row in the whole gallery, when asked for, is passes 2 and 3 with gt = best_idx.  Rows are scaled by
 // 1 / max(norm, eps) (sim_matrix, accuracy.py:385-394); eps = 0 is the normalisation above.
+//
+// Dual-softmax re-scoring (clv_retrieval_col_stats + clv_retrieval_rank_prior): s'[i][j] = s[i][j] * softmax_i(T s[i][j]),
+// the softmax taken down the QUERY axis, so every query is coupled to every other one through the column statistics
+//     m_j = max_i T s[i][j],   l_j = sum_i exp(T s[i][j] - m_j).
+// retrieval_score_kernel<RT_STATS> is pass 3's tile loop with the operands swapped: its "queries" are the gallery rows (a
+// workgroup owns 64 of them) and it walks the query set in 64-row tiles.  fmaf(a, b, c) == fmaf(b, a, c) and the order of k
+// is the same, so the transposed score is bit-equal to s[i][j].  Every lane keeps a running (m, l) for its 8 rows; they
+// meet over the 16 lanes of a row by xor shuffles, over the two waves of a row through LDS, and over the chunks of a long
+// query set in retrieval_stats_merge_kernel, which joins the partials in chunk order: no float atomics, one fixed order.
+// clv_retrieval_rank_prior is passes 1-4 with PRIOR = true: wherever a score leaves the accumulators it becomes
+// rt_prior(s, m_j, l_j, T) first — in pass 2 for gt_score, in pass 3 for the counts and the lists — by one inlined
+// function without contraction, so pass 3 meets pass 2's gt_score bit for bit as before.
 #include "common.hpp"
 #include "../../include/clover_hip.h"
 
@@ -45,8 +57,9 @@ constexpr int RT_KMAX = 16, RT_LLD = RT_KMAX + 1;
 constexpr int RT_MAX_CHUNKS = 64;          // bounds the top-K partial table: chunks x Nq x K x 8 bytes
 constexpr int RT_WANT_GROUPS = 512;        // two workgroups per CU before the gallery stops being split
 
-enum { RT_GT = 0, RT_COUNT = 1, RT_TOPK = 2, RT_BEST = 3 };
+enum { RT_GT = 0, RT_COUNT = 1, RT_TOPK = 2, RT_BEST = 3, RT_STATS = 4 };
 constexpr const int32_t* RT_ALL = nullptr;   // lo / hi of the modes that have no ranges
+constexpr const float* RT_PLAIN = nullptr;   // col_max / col_sum of the launches without the prior
 
 struct RtPlan {
     int nqb, tiles, tiles_per_chunk, chunks;
@@ -81,22 +94,54 @@ __global__ void __launch_bounds__(256) retrieval_normalize_kernel(const float* _
     for (int d = lane; d < D; d += 64) o[d] = e[d] / nrm;
 }
 
+// (m, l) <- (m, l) joined with (m2, l2), both an online max / sum of exponentials: l counts exp(x - m).  An empty side is
+// (-inf, 0); two empty sides stay empty (no inf - inf).
+__device__ __forceinline__ void rt_stat_join(float& m, float& l, float m2, float l2) {
+#pragma clang fp contract(off)
+    const float mm = fmaxf(m, m2);
+    if (mm == -INFINITY) return;
+    l = l * expf(m - mm) + l2 * expf(m2 - mm);
+    m = mm;
+}
+
+// two more exponents (-inf: a masked column) into a lane's running (m, l)
+__device__ __forceinline__ void rt_stat_add2(float& m, float& l, float x0, float x1) {
+#pragma clang fp contract(off)
+    const float mm = fmaxf(m, fmaxf(x0, x1));
+    if (mm == -INFINITY) return;
+    l = l * expf(m - mm) + expf(x0 - mm) + expf(x1 - mm);
+    m = mm;
+}
+
+// the re-scored value: one rounding per operation (T * s is the product col_stats took the maximum of)
+__device__ __forceinline__ float rt_prior(float s, float m, float l, float T) {
+#pragma clang fp contract(off)
+    const float x = T * s;
+    return s * expf(x - m) / l;
+}
+
 // qn [Nq][D], gn [Ng][D] packed unit rows.  Grid: (query blocks, gallery chunks); RT_GT: (query blocks, 1).
 // RT_BEST reads lo / hi [Nq] (both null: the whole gallery) and writes part_score / part_idx [chunks][Nq]: the first
 // maximum of query m over the columns of this chunk inside [lo[m], hi[m]), or -inf / -1 when there is none.
-template <int MODE>
+// PRIOR (RT_GT, RT_COUNT, RT_TOPK): col_max / col_sum [Ng] and T turn every score into rt_prior(...) before it is kept,
+// compared or listed.  RT_STATS is launched with the operands swapped (qn = the gallery's rows, Nq = their number; gn =
+// the queries) and writes part_score [chunks][Nq][2]: (max, sum) of T * s over the columns of this chunk.
+template <int MODE, bool PRIOR = false>
 __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __restrict__ qn, const float* __restrict__ gn,
                                                               const int32_t* __restrict__ gt, int32_t* __restrict__ rank,
                                                               float* __restrict__ gt_score, float* __restrict__ part_score,
                                                               int32_t* __restrict__ part_idx, int Nq, int Ng, int D,
                                                               int tiles_per_chunk, int topk,
                                                               const int32_t* __restrict__ lo,
-                                                              const int32_t* __restrict__ hi) {
+                                                              const int32_t* __restrict__ hi,
+                                                              const float* __restrict__ col_max,
+                                                              const float* __restrict__ col_sum, float T) {
     __shared__ float As[RT_BM * RT_LD], Bs[RT_BN * RT_LD];
     __shared__ float Ss[(MODE == RT_TOPK || MODE == RT_BEST) ? RT_BM * RT_SLD : 1];
     __shared__ int Span[MODE == RT_BEST ? 2 : 1];
     __shared__ float Ls[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
     __shared__ int32_t Li[MODE == RT_TOPK ? RT_BM * RT_LLD : 1];
+    __shared__ float Sm[MODE == RT_STATS ? 2 * RT_BM : 1], Sl[MODE == RT_STATS ? 2 * RT_BM : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lg = lane >> 4, lr = lane & 15;
     const int m0 = blockIdx.x * RT_BM;
@@ -124,6 +169,16 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
                 g[i][r] = truth(m);
                 gs[i][r] = g[i][r] >= 0 ? gt_score[m] : 0.f;
                 cnt[i][r] = 0;
+            }
+    }
+    float sm[2][4], sl[2][4];                                // RT_STATS: the lane's running (m, l) of its 8 rows
+    if (MODE == RT_STATS) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                sm[i][r] = -INFINITY;
+                sl[i][r] = 0.f;
             }
     }
     if (MODE == RT_TOPK) {
@@ -217,12 +272,24 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
                     for (int r = 0; r < 4; ++r) {
                         const int m = m0 + wr + i * 16 + lg * 4 + r;
                         if (lg * 4 + r == lr && m < Nq) {
-                            const bool ok = truth(m) >= 0;
-                            gt_score[m] = ok ? acc[i][i][r] : __builtin_nanf("");
+                            const int gg = truth(m);
+                            const bool ok = gg >= 0;
+                            float s = acc[i][i][r];
+                            if (PRIOR && ok) s = rt_prior(s, col_max[gg], col_sum[gg], T);
+                            gt_score[m] = ok ? s : __builtin_nanf("");
                             rank[m] = ok ? 0 : -1;
                         }
                     }
             }
+        } else if (MODE == RT_STATS) {
+            // the columns of this launch are the queries: Ng is their number, and a padded one adds nothing
+            const bool in0 = n0 + wc + lr < Ng, in1 = n0 + wc + 16 + lr < Ng;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    rt_stat_add2(sm[i][r], sl[i][r], in0 ? T * acc[i][0][r] : -INFINITY,
+                                 in1 ? T * acc[i][1][r] : -INFINITY);
         } else if (MODE == RT_BEST) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -250,9 +317,11 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int jg = n0 + wc + j * 16 + lr;
+                    const float cm = (PRIOR && jg < Ng) ? col_max[jg] : 0.f;
+                    const float cl = (PRIOR && jg < Ng) ? col_sum[jg] : 1.f;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float s = acc[i][j][r];
+                        const float s = PRIOR ? rt_prior(acc[i][j][r], cm, cl, T) : acc[i][j][r];
                         const bool ahead = s > gs[i][r] || (s == gs[i][r] && jg < g[i][r]);
                         cnt[i][r] += (jg < Ng && jg != g[i][r] && ahead) ? 1 : 0;
                         if (MODE == RT_TOPK) Ss[(wr + i * 16 + lg * 4 + r) * RT_SLD + wc + j * 16 + lr] = s;
@@ -285,6 +354,28 @@ __global__ void __launch_bounds__(256) retrieval_score_kernel(const float* __res
         }
     }
 
+    if (MODE == RT_STATS) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1)              // the 16 lanes that share the row: both partners get the same sum
+                    rt_stat_join(sm[i][r], sl[i][r], __shfl_xor(sm[i][r], o, 64), __shfl_xor(sl[i][r], o, 64));
+                if (lr == 0) {
+                    Sm[(wave & 1) * RT_BM + wr + i * 16 + lg * 4 + r] = sm[i][r];
+                    Sl[(wave & 1) * RT_BM + wr + i * 16 + lg * 4 + r] = sl[i][r];
+                }
+            }
+        __syncthreads();
+        if (tid < RT_BM && m0 + tid < Nq) {                   // columns 0..31 of every tile, then columns 32..63
+            float m = Sm[tid], l = Sl[tid];
+            rt_stat_join(m, l, Sm[RT_BM + tid], Sl[RT_BM + tid]);
+            const int64_t at = ((int64_t)blockIdx.y * Nq + m0 + tid) * 2;
+            part_score[at] = m;
+            part_score[at + 1] = l;
+        }
+    }
     if (MODE == RT_BEST) {
         if (tid < RT_BM && m0 + tid < Nq) {
             part_score[(int64_t)blockIdx.y * Nq + m0 + tid] = bscore;
@@ -382,9 +473,64 @@ __global__ void __launch_bounds__(256) retrieval_best_merge_kernel(const float* 
     best_score[i] = bi >= 0 ? bs : __builtin_nanf("");
 }
 
+// one thread per gallery row: the chunk partials (max, sum) joined in chunk order.  Every chunk holds at least one query,
+// so every partial is finite and col_sum >= 1.
+__global__ void __launch_bounds__(256) retrieval_stats_merge_kernel(const float* __restrict__ part, float* __restrict__ col_max,
+                                                                    float* __restrict__ col_sum, int Ng, int chunks) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= Ng) return;
+    float m = -INFINITY, l = 0.f;
+    for (int c = 0; c < chunks; ++c) {
+        const int64_t at = ((int64_t)c * Ng + j) * 2;
+        rt_stat_join(m, l, part[at], part[at + 1]);
+    }
+    col_max[j] = m;
+    col_sum[j] = l;
+}
+
 inline bool rt_supported(int64_t Nq, int64_t Ng, int32_t D, int32_t topk) {
     return Nq >= 1 && Ng >= 1 && Nq <= 0x7fffffff - RT_BM && Ng <= 0x7fffffff - RT_BN && D >= 4 && D <= 4096 &&
            D % 4 == 0 && topk >= 0 && topk <= RT_KMAX;
+}
+
+// T finite and >= 0 (a NaN fails both)
+inline bool rt_temperature_ok(float T) { return T >= 0.f && T <= 3.402823466e38f; }
+
+// clv_retrieval_rank (PRIOR = false: col_max, col_sum and T are not read) and clv_retrieval_rank_prior: the same launches
+template <bool PRIOR>
+int rt_rank(const float* query, const float* gallery, const int32_t* gt, int32_t* rank, float* gt_score, int32_t* topk_idx,
+            float* topk_score, void* work, int64_t Nq, int64_t Ng, int32_t D, int64_t ldq, int64_t ldg, int32_t topk,
+            const float* col_max, const float* col_sum, float T, void* stream) {
+    if (!rt_supported(Nq, Ng, D, topk)) return CLV_ERR_UNSUPPORTED;
+    if (!query || !gallery || !rank || !gt_score || !work || ldq < D || ldg < D) return CLV_ERR_ARG;
+    if (topk > 0 && (!topk_idx || !topk_score)) return CLV_ERR_ARG;
+    if (!gt && Nq > Ng) return CLV_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return CLV_ERR_ARG;
+    if (PRIOR && (!col_max || !col_sum || !rt_temperature_ok(T))) return CLV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const RtPlan p = rt_plan(Nq, Ng);
+    float* qn = (float*)work;
+    float* gn = qn + Nq * (int64_t)D;
+    float* part_score = gn + Ng * (int64_t)D;
+    int32_t* part_idx = (int32_t*)(part_score + (int64_t)p.chunks * Nq * topk);
+    const int64_t rows = Nq + Ng;
+    hipLaunchKernelGGL(retrieval_normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, query, gallery, qn,
+                       Nq, Ng, (int)D, ldq, ldg, 0.f);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(retrieval_score_kernel<RT_GT, PRIOR>), dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, gt,
+                       rank, gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0, RT_ALL, RT_ALL,
+                       col_max, col_sum, T);
+    if (topk > 0) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(retrieval_score_kernel<RT_TOPK, PRIOR>), dim3(p.nqb, p.chunks), dim3(256), 0, st,
+                           qn, gn, gt, rank, gt_score, part_score, part_idx, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk,
+                           (int)topk, RT_ALL, RT_ALL, col_max, col_sum, T);
+        hipLaunchKernelGGL(retrieval_topk_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
+                           part_idx, topk_idx, topk_score, (int)Nq, p.chunks, (int)topk);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(retrieval_score_kernel<RT_COUNT, PRIOR>), dim3(p.nqb, p.chunks), dim3(256), 0, st,
+                           qn, gn, gt, rank, gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D,
+                           p.tiles_per_chunk, 0, RT_ALL, RT_ALL, col_max, col_sum, T);
+    }
+    return clv_check_launch();
 }
 
 }  // namespace
@@ -398,34 +544,48 @@ extern "C" int64_t clv_retrieval_work_bytes(int64_t Nq, int64_t Ng, int32_t D, i
 extern "C" int clv_retrieval_rank(const float* query, const float* gallery, const int32_t* gt, int32_t* rank,
                                   float* gt_score, int32_t* topk_idx, float* topk_score, void* work, int64_t Nq,
                                   int64_t Ng, int32_t D, int64_t ldq, int64_t ldg, int32_t topk, void* stream) {
-    if (!rt_supported(Nq, Ng, D, topk)) return CLV_ERR_UNSUPPORTED;
-    if (!query || !gallery || !rank || !gt_score || !work || ldq < D || ldg < D) return CLV_ERR_ARG;
-    if (topk > 0 && (!topk_idx || !topk_score)) return CLV_ERR_ARG;
-    if (!gt && Nq > Ng) return CLV_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return CLV_ERR_ARG;
+    return rt_rank<false>(query, gallery, gt, rank, gt_score, topk_idx, topk_score, work, Nq, Ng, D, ldq, ldg, topk, RT_PLAIN,
+                          RT_PLAIN, 0.f, stream);
+}
+
+extern "C" int64_t clv_retrieval_col_stats_work_bytes(int64_t Nq, int64_t Ng, int32_t D) {
+    if (!rt_supported(Nq, Ng, D, 0)) return CLV_ERR_UNSUPPORTED;
+    const RtPlan p = rt_plan(Ng, Nq);                         // the gallery rows own the workgroups, the queries are walked
+    return (Nq + Ng) * (int64_t)D * 4 + (int64_t)p.chunks * Ng * 8;
+}
+
+extern "C" int clv_retrieval_col_stats(const float* query, const float* gallery, int64_t Nq, int64_t Ng, int32_t D,
+                                       int64_t ldq, int64_t ldg, float T, float* col_max, float* col_sum, void* work,
+                                       void* stream) {
+    if (!rt_supported(Nq, Ng, D, 0)) return CLV_ERR_UNSUPPORTED;
+    if (!query || !gallery || !col_max || !col_sum || !work || ldq < D || ldg < D) return CLV_ERR_ARG;
+    if (!rt_temperature_ok(T) || reinterpret_cast<uintptr_t>(work) % 16 != 0) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const RtPlan p = rt_plan(Nq, Ng);
+    const RtPlan p = rt_plan(Ng, Nq);
     float* qn = (float*)work;
     float* gn = qn + Nq * (int64_t)D;
-    float* part_score = gn + Ng * (int64_t)D;
-    int32_t* part_idx = (int32_t*)(part_score + (int64_t)p.chunks * Nq * topk);
+    float* part = gn + Ng * (int64_t)D;
     const int64_t rows = Nq + Ng;
     hipLaunchKernelGGL(retrieval_normalize_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, query, gallery, qn,
                        Nq, Ng, (int)D, ldq, ldg, 0.f);
-    hipLaunchKernelGGL(retrieval_score_kernel<RT_GT>, dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, gt, rank, gt_score,
-                       (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0, RT_ALL, RT_ALL);
-    if (topk > 0) {
-        hipLaunchKernelGGL(retrieval_score_kernel<RT_TOPK>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
-                           gt_score, part_score, part_idx, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, (int)topk, RT_ALL,
-                           RT_ALL);
-        hipLaunchKernelGGL(retrieval_topk_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
-                           part_idx, topk_idx, topk_score, (int)Nq, p.chunks, (int)topk);
-    } else {
-        hipLaunchKernelGGL(retrieval_score_kernel<RT_COUNT>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn, gt, rank,
-                           gt_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, p.tiles_per_chunk, 0,
-                           RT_ALL, RT_ALL);
-    }
+    hipLaunchKernelGGL(retrieval_score_kernel<RT_STATS>, dim3(p.nqb, p.chunks), dim3(256), 0, st, (const float*)gn,
+                       (const float*)qn, (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, part,
+                       (int32_t*)nullptr, (int)Ng, (int)Nq, (int)D, p.tiles_per_chunk, 0, RT_ALL, RT_ALL, RT_PLAIN, RT_PLAIN, T);
+    hipLaunchKernelGGL(retrieval_stats_merge_kernel, dim3((unsigned)((Ng + 255) / 256)), dim3(256), 0, st, (const float*)part,
+                       col_max, col_sum, (int)Ng, p.chunks);
     return clv_check_launch();
+}
+
+extern "C" int64_t clv_retrieval_rank_prior_work_bytes(int64_t Nq, int64_t Ng, int32_t D, int32_t topk) {
+    return clv_retrieval_work_bytes(Nq, Ng, D, topk);
+}
+
+extern "C" int clv_retrieval_rank_prior(const float* query, const float* gallery, const int32_t* gt, int32_t* rank,
+                                        float* gt_score, int32_t* topk_idx, float* topk_score, void* work, int64_t Nq,
+                                        int64_t Ng, int32_t D, int64_t ldq, int64_t ldg, int32_t topk, const float* col_max,
+                                        const float* col_sum, float T, void* stream) {
+    return rt_rank<true>(query, gallery, gt, rank, gt_score, topk_idx, topk_score, work, Nq, Ng, D, ldq, ldg, topk, col_max,
+                         col_sum, T, stream);
 }
 
 extern "C" int64_t clv_retrieval_group_work_bytes(int64_t Nq, int64_t Ng, int32_t D) {
@@ -452,7 +612,7 @@ extern "C" int clv_retrieval_group_best(const float* query, const float* gallery
                        Nq, Ng, (int)D, ldq, ldg, eps);
     hipLaunchKernelGGL(retrieval_score_kernel<RT_BEST>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn,
                        (const int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, part_score, part_idx, (int)Nq, (int)Ng,
-                       (int)D, p.tiles_per_chunk, 0, lo, hi);
+                       (int)D, p.tiles_per_chunk, 0, lo, hi, RT_PLAIN, RT_PLAIN, 0.f);
     hipLaunchKernelGGL(retrieval_best_merge_kernel, dim3((unsigned)((Nq + 255) / 256)), dim3(256), 0, st, part_score,
                        part_idx, best_idx, best_score, (int)Nq, p.chunks);
     if (rank) {
@@ -460,10 +620,10 @@ extern "C" int clv_retrieval_group_best(const float* query, const float* gallery
         // same two rows in the same k order, so the same bits (and NaN where best_idx = -1).
         hipLaunchKernelGGL(retrieval_score_kernel<RT_GT>, dim3(p.nqb, 1), dim3(256), 0, st, qn, gn, (const int32_t*)best_idx,
                            rank, best_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng, (int)D, 1, 0, RT_ALL,
-                           RT_ALL);
+                           RT_ALL, RT_PLAIN, RT_PLAIN, 0.f);
         hipLaunchKernelGGL(retrieval_score_kernel<RT_COUNT>, dim3(p.nqb, p.chunks), dim3(256), 0, st, qn, gn,
                            (const int32_t*)best_idx, rank, best_score, (float*)nullptr, (int32_t*)nullptr, (int)Nq, (int)Ng,
-                           (int)D, p.tiles_per_chunk, 0, RT_ALL, RT_ALL);
+                           (int)D, p.tiles_per_chunk, 0, RT_ALL, RT_ALL, RT_PLAIN, RT_PLAIN, 0.f);
     }
     return clv_check_launch();
 }

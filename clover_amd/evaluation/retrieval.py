@@ -12,6 +12,11 @@ Zero-shot multiple choice (``acc_for_msrvtt_mc``, accuracy.py:396-427) and the m
 (``recall_for_video_text_retrieval_varied``, accuracy.py:465-523, with its test loop my_eval_hook.py:115-215) are here the
 same way: a numpy restatement for host results, and ``mc_acc_on_device`` / ``recall_varied_on_device`` on
 ``ops.retrieval_group_best`` / ``ops.retrieval_rank`` for device results.
+
+Dual-softmax re-scoring at inference (``dual_softmax=T``; NOT in the reference): every score is multiplied by a softmax
+prior taken over all queries for its gallery item, ``s' = s * softmax(T * s, axis=0)``, which damps hub videos.  It is an
+opt-in that ADDS ``DSL_*`` keys next to the plain ones: ``dual_softmax_scores`` for host results,
+``ops.retrieval_rank(..., dual_softmax=T)`` for device results.
 """
 import numpy as np
 
@@ -24,10 +29,37 @@ def normalize_fn(x, axis=-1, order=2):
     return x / np.expand_dims(l2, axis=axis)
 
 
-def recall_for_video_text_retrieval(video_embd=None, text_embd=None, input_scores=None, use_sim=False, texts=None):
+def dual_softmax_scores(scores, T):
+    """``s'[i][j] = s[i][j] * softmax_i(T * s[i][j])`` for a host score matrix [Nq, Ng]: the softmax runs down the QUERY
+    axis (axis 0), the column maximum is subtracted before ``exp``.  Computed in the dtype of ``scores``."""
+    s = np.asarray(scores)
+    T = float(T)
+    if not (T >= 0 and np.isfinite(T)):
+        raise ValueError(f'dual_softmax: T must be finite and >= 0 (got {T})')
+    x = s * s.dtype.type(T)
+    e = np.exp(x - x.max(axis=0, keepdims=True))
+    return s * e / e.sum(axis=0, keepdims=True)
+
+
+def _dsl_ranks(scores, gt, T):
+    """Ranks of the ground truth under the re-scored matrix, ties by index (the device path's rule)."""
+    order = np.argsort(-dual_softmax_scores(scores, T), axis=1, kind='stable')
+    return np.where(order == np.asarray(gt)[:, None])[1]
+
+
+def _dsl_keys(ind, with_all=False):
+    out = _recall_keys(ind, 'DSL_')
+    if with_all:
+        out['DSL_Recall@all'] = out['DSL_Recall@1'] + out['DSL_Recall@5'] + out['DSL_Recall@10'] - out['DSL_MR']
+    return out
+
+
+def recall_for_video_text_retrieval(video_embd=None, text_embd=None, input_scores=None, use_sim=False, texts=None,
+                                    dual_softmax=None):
     """R@1 / R@5 / R@10 (percent), median rank (1-based) and ``Recall@all`` = R1 + R5 + R10 - MR of
     text -> video retrieval; query i's ground truth is video i.  ``use_sim`` is accepted and ignored, as in the
-    reference (accuracy.py:438 overwrites it with False); ``texts`` is unused there too."""
+    reference (accuracy.py:438 overwrites it with False); ``texts`` is unused there too.  ``dual_softmax = T`` adds the
+    same five keys with the prefix ``DSL_``, from ``dual_softmax_scores(scores, T)``; the plain keys do not change."""
     if input_scores is not None:
         scores = np.asarray(input_scores)
     else:
@@ -42,16 +74,21 @@ def recall_for_video_text_retrieval(video_embd=None, text_embd=None, input_score
         'MR': np.median(ind) + 1,
     }
     metrics['Recall@all'] = metrics['Recall@1'] + metrics['Recall@5'] + metrics['Recall@10'] - metrics['MR']
+    if dual_softmax is not None:
+        metrics.update(_dsl_keys(_dsl_ranks(scores, gt, dual_softmax), with_all=True))
     return metrics
 
 
-def recall_on_device(video_embd, text_embd, gt=None, topk=0):
+def recall_on_device(video_embd, text_embd, gt=None, topk=0, dual_softmax=None):
     """``recall_for_video_text_retrieval`` with the scoring on the device: the same five keys, from the ranks
     ``ops.retrieval_rank`` returns; only that [Nq] int32 vector (and the [Nq, topk] indices asked for) crosses to the
     host, the median and the counts stay numpy.  ``video_embd`` fp32 [N, D] is the gallery; ``text_embd`` [Nq, D] the
     queries, or [N, C, D] — C captions per video — which means Nq = N * C queries with ``gt = i // C``.  ``gt`` None:
     query i's ground truth is video i.  Ties rank by index (the stable order); queries with ``gt < 0`` are left out.
-    With ``topk`` the result also carries ``'topk'``: int array [Nq, topk], the retrieved video indices per query."""
+    With ``topk`` the result also carries ``'topk'``: int array [Nq, topk], the retrieved video indices per query.
+    ``dual_softmax = T`` runs the ranks a second time under the dual-softmax prior (``ops.retrieval_rank(...,
+    dual_softmax=T)``: the prior spans all Nq queries of this call) and ADDS ``DSL_Recall@1/5/10``, ``DSL_MR`` and
+    ``DSL_Recall@all``, with ``topk`` also ``'dsl_topk'``; every plain key, ``'topk'`` included, stays what it is."""
     import torch
     from .. import ops
     v, t = torch.as_tensor(video_embd), torch.as_tensor(text_embd)
@@ -75,6 +112,12 @@ def recall_on_device(video_embd, text_embd, gt=None, topk=0):
     metrics['Recall@all'] = metrics['Recall@1'] + metrics['Recall@5'] + metrics['Recall@10'] - metrics['MR']
     if topk:
         metrics['topk'] = tidx.cpu().numpy()
+    if dual_softmax is not None:
+        drank, _, didx, _ = ops.retrieval_rank(t.float(), v.float(), gt=gt, topk=topk, dual_softmax=dual_softmax)
+        dind = drank.cpu().numpy()
+        metrics.update(_dsl_keys(dind[dind >= 0], with_all=True))
+        if topk:
+            metrics['dsl_topk'] = didx.cpu().numpy()
     return metrics
 
 
@@ -111,25 +154,38 @@ def acc_for_msrvtt_mc(video_embd, text_embd, label, use_sim=True):
     return {'acc': float((ans == label).astype(np.float32).mean())}
 
 
-def recall_for_video_text_retrieval_varied(video_embd, text_embd, tid):
+def recall_for_video_text_retrieval_varied(video_embd, text_embd, tid, dual_softmax=None):
     """Text -> video R@1 / R@5 / R@10 (percent) and median rank (1-based) when video i has ``len(tid[i])`` captions
     (accuracy.py:465-523): ``text_embd`` [sum of the lengths, D] holds the captions video by video, every caption's ground
     truth is its video; scores by ``sim_matrix``.  Of ``tid`` only the per-video lengths are used (an int sequence of
     counts is taken as it is).  No ``Recall@all``, as there.  Equal scores rank by video index (a stable sort, which
-    is also the device path's rule; the reference's ``np.argsort`` leaves their order open)."""
+    is also the device path's rule; the reference's ``np.argsort`` leaves their order open).  ``dual_softmax = T`` adds
+    ``DSL_Recall@1/5/10`` and ``DSL_MR`` from ``dual_softmax_scores(scores, T)`` (the prior over all captions)."""
     counts = np.array([t if np.ndim(t) == 0 else len(t) for t in tid], dtype=np.int64)
     scores = sim_matrix(_host(text_embd), _host(video_embd))
     order = np.argsort(-scores, axis=1, kind='stable')
     gt = np.repeat(np.arange(len(counts)), counts)
     ind = np.where(order == gt[:, None])[1]
-    return _recall_keys(ind)
+    out = _recall_keys(ind)
+    if dual_softmax is not None:
+        out.update(_dsl_keys(_dsl_ranks(scores, gt, dual_softmax)))
+    return out
 
 
-def mc_acc_on_device(video_embd, text_embd, label, return_pred=False):
+_NO_DSL_MC = ('dual_softmax is not defined for multiple choice (video_qa_mc / mc_acc_on_device): every video scores its own '
+              'candidates only, and a prior over candidates that belong to different videos has no meaning')
+_NO_DSL_V2T = ('dual_softmax does not cover the V2T_* keys of recall_varied_on_device: video -> text would need the prior '
+               'inside clv_retrieval_group_best; ask for v2t without dual_softmax (the V2T_* keys are plain scores)')
+
+
+def mc_acc_on_device(video_embd, text_embd, label, return_pred=False, dual_softmax=None):
     """``acc_for_msrvtt_mc`` with the scoring on the device: one ``ops.retrieval_group_best`` call in which video i
     looks at the text rows [i*C, (i+1)*C) only (``eps = 1e-8`` as ``sim_matrix``), so of the N x N*C scores the reference
     computes only the N x C it keeps are; ``pred = best_idx - i*C`` [N] is all that crosses to the host.  ``text_embd``
-    fp32 [N, C, D] or [N*C, D].  -> ``{'acc'}`` (the float32 mean, as there), with ``return_pred`` also ``'pred'``."""
+    fp32 [N, C, D] or [N*C, D].  -> ``{'acc'}`` (the float32 mean, as there), with ``return_pred`` also ``'pred'``.
+    ``dual_softmax`` is refused: it is not defined here."""
+    if dual_softmax is not None:
+        raise ValueError(_NO_DSL_MC)
     import torch
     from .. import ops
     v, t = torch.as_tensor(video_embd).float(), torch.as_tensor(text_embd).float()
@@ -147,7 +203,7 @@ def mc_acc_on_device(video_embd, text_embd, label, return_pred=False):
     return out
 
 
-def recall_varied_on_device(video_embd, text_embd, counts, v2t=False):
+def recall_varied_on_device(video_embd, text_embd, counts, v2t=False, dual_softmax=None):
     """``recall_for_video_text_retrieval_varied`` with the scoring on the device.  ``video_embd`` fp32 [N, D],
     ``text_embd`` [sum(counts), D] video by video, ``counts`` int [N].  Text -> video (the reference's four keys) comes
     from ``ops.retrieval_rank`` with ``gt = repeat_interleave(arange(N), counts)``; rows are normalised as ``normalize_fn``
@@ -157,7 +213,12 @@ def recall_varied_on_device(video_embd, text_embd, counts, v2t=False):
     best of its own captions (``ops.retrieval_group_best(video, text, lo, hi, want_rank=True)``, the ranges from
     ``cumsum(counts)``).  That is the usual best-caption protocol of video -> text retrieval (the minimum rank over a
     video's valid descriptions); it has NO counterpart in the reference, whose function scores text -> video only.
-    Only the int32 rank vectors cross to the host."""
+    Only the int32 rank vectors cross to the host.
+
+    ``dual_softmax = T`` ADDS ``DSL_Recall@1/5/10`` and ``DSL_MR`` (text -> video under the prior over all captions,
+    ``ops.retrieval_rank(..., dual_softmax=T)``); the plain keys stay.  Together with ``v2t`` it is refused."""
+    if dual_softmax is not None and v2t:
+        raise ValueError(_NO_DSL_V2T)
     import torch
     from .. import ops
     v, t = torch.as_tensor(video_embd).float(), torch.as_tensor(text_embd).float()
@@ -168,6 +229,9 @@ def recall_varied_on_device(video_embd, text_embd, counts, v2t=False):
     gt = torch.repeat_interleave(torch.arange(v.shape[0], device=v.device), counts).to(torch.int32)
     rank, _, _, _ = ops.retrieval_rank(t, v, gt=gt)
     out = _recall_keys(rank.cpu().numpy())
+    if dual_softmax is not None:
+        drank, _, _, _ = ops.retrieval_rank(t, v, gt=gt, dual_softmax=dual_softmax)
+        out.update(_dsl_keys(drank.cpu().numpy()))
     if v2t:
         hi = torch.cumsum(counts, 0)
         _, _, vrank = ops.retrieval_group_best(v, t, hi - counts, hi, want_rank=True)
@@ -311,14 +375,22 @@ def multi_gpu_test_retrieval_varied(model, data_loader, to_host=True):
 RETRIEVAL_METRICS = ('recall_for_video_text_retrieval', 'video_qa_mc', 'recall_for_video_text_retrieval_varied')
 
 
-def evaluate_retrieval(results, metrics=('recall_for_video_text_retrieval',), topk=0, with_pred=False, v2t=False):
+def evaluate_retrieval(results, metrics=('recall_for_video_text_retrieval',), topk=0, with_pred=False, v2t=False,
+                       dual_softmax=None):
     """The embedding-similarity branches of ``VideoDataset.evaluate`` (mmaction/datasets/video_dataset.py:173-182
     ``video_qa_mc``, needs ``results['label']``; :189-195 ``recall_for_video_text_retrieval``; :196-203
     ``recall_for_video_text_retrieval_varied``, needs ``results['counts']``).  Results that hold device tensors (the
     test loops with ``to_host=False``) are scored on the device (``recall_on_device``, which is also what ``topk``
     needs; ``mc_acc_on_device``, which is what ``with_pred`` — the chosen candidate per video as ``'pred'`` — needs;
-    ``recall_varied_on_device``, which is what ``v2t`` needs); numpy results take the reference's host path."""
+    ``recall_varied_on_device``, which is what ``v2t`` needs); numpy results take the reference's host path.
+    ``dual_softmax = T`` adds the ``DSL_*`` keys of the two recall metrics on either path (with ``topk`` also
+    ``'dsl_topk'``); ``video_qa_mc`` and ``v2t`` refuse it."""
     out = {}
+    names = [metrics] if isinstance(metrics, str) else list(metrics)
+    if dual_softmax is not None and 'video_qa_mc' in names:
+        raise ValueError(_NO_DSL_MC)
+    if dual_softmax is not None and v2t:
+        raise ValueError(_NO_DSL_V2T)
     v = results['video_embd']
     on_device = getattr(v, 'is_cuda', False)
     if (topk or with_pred or v2t) and not on_device:
@@ -335,14 +407,15 @@ def evaluate_retrieval(results, metrics=('recall_for_video_text_retrieval',), to
             continue
         if metric == 'recall_for_video_text_retrieval_varied':
             if on_device:
-                out.update(recall_varied_on_device(v, results['text_embd'], results['counts'], v2t=v2t))
+                out.update(recall_varied_on_device(v, results['text_embd'], results['counts'], v2t=v2t,
+                                                   dual_softmax=dual_softmax))
             else:
                 out.update(recall_for_video_text_retrieval_varied(np.stack(list(v)), results['text_embd'],
-                                                                  results['counts']))
+                                                                  results['counts'], dual_softmax=dual_softmax))
             continue
         if on_device:
-            out.update(recall_on_device(v, results['text_embd'], topk=topk))
+            out.update(recall_on_device(v, results['text_embd'], topk=topk, dual_softmax=dual_softmax))
             continue
         out.update(recall_for_video_text_retrieval(np.stack(list(results['video_embd'])),
-                                                   np.stack(list(results['text_embd']))))
+                                                   np.stack(list(results['text_embd'])), dual_softmax=dual_softmax))
     return out

@@ -2982,12 +2982,15 @@ def attn_probs_mean(qkv, kmask, num_heads):
     return out
 
 
-def retrieval_rank(query, gallery, gt=None, topk=0):
+def retrieval_rank(query, gallery, gt=None, topk=0, dual_softmax=None):
     """Retrieval ranks on the device (clv_retrieval_rank; accuracy.py:430-462 without the score matrix or the sort).
     query fp32 [Nq, D], gallery fp32 [Ng, D] (rows are normalised inside, all-zero rows stay zero), gt int [Nq] = each
     query's ground-truth gallery row (None: query i <-> row i) ->
     (rank int32 [Nq]: 0-based position of the ground truth in the stable descending order of the query's scores, -1 where
     gt < 0;  gt_score fp32 [Nq];  topk_idx int32 [Nq, topk] and topk_score fp32 [Nq, topk], or None, None with topk = 0).
+    dual_softmax = T (a float >= 0): the order, gt_score and topk_score are those of the re-scored
+    s'[i][j] = s[i][j] * softmax_i(T * s[i][j]) — the softmax over ALL queries of this call, per gallery row
+    (clv_retrieval_col_stats, then clv_retrieval_rank_prior; O(Ng) extra memory).  None: the plain scores.
     Inference only: no autograd."""
     _need_gpu(query, gallery, gt)
     if query.dtype != torch.float32 or gallery.dtype != torch.float32:
@@ -3008,15 +3011,56 @@ def retrieval_rank(query, gallery, gt=None, topk=0):
     L = _lib.lib()
     nbytes = L.clv_retrieval_work_bytes(Nq, Ng, D, topk)
     check(min(nbytes, 0), 'clv_retrieval_work_bytes')
+    if dual_softmax is not None:                       # one area serves the statistics pass and then the rank pass
+        sbytes = L.clv_retrieval_col_stats_work_bytes(Nq, Ng, D)
+        check(min(sbytes, 0), 'clv_retrieval_col_stats_work_bytes')
+        nbytes = max(nbytes, sbytes)
     dev = q.device
     work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     rank = torch.empty(Nq, device=dev, dtype=torch.int32)
     gscore = torch.empty(Nq, device=dev, dtype=torch.float32)
     tidx = torch.empty(Nq, topk, device=dev, dtype=torch.int32) if topk else None
     tscore = torch.empty(Nq, topk, device=dev, dtype=torch.float32) if topk else None
+    if dual_softmax is not None:
+        T = float(dual_softmax)
+        cmax = torch.empty(Ng, device=dev, dtype=torch.float32)
+        csum = torch.empty(Ng, device=dev, dtype=torch.float32)
+        ldq, ldg = max(q.stride(0), D), max(g.stride(0), D)
+        check(L.clv_retrieval_col_stats(_ptr(q), _ptr(g), Nq, Ng, D, ldq, ldg, T, _ptr(cmax), _ptr(csum), _ptr(work),
+                                        _stream()), 'clv_retrieval_col_stats')
+        check(L.clv_retrieval_rank_prior(_ptr(q), _ptr(g), _ptr(gt), _ptr(rank), _ptr(gscore), _ptr(tidx), _ptr(tscore),
+                                         _ptr(work), Nq, Ng, D, ldq, ldg, topk, _ptr(cmax), _ptr(csum), T, _stream()),
+              'clv_retrieval_rank_prior')
+        return rank, gscore, tidx, tscore
     check(L.clv_retrieval_rank(_ptr(q), _ptr(g), _ptr(gt), _ptr(rank), _ptr(gscore), _ptr(tidx), _ptr(tscore), _ptr(work),
                                Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), topk, _stream()), 'clv_retrieval_rank')
     return rank, gscore, tidx, tscore
+
+
+def retrieval_col_stats(query, gallery, T):
+    """The column statistics of the dual-softmax prior (clv_retrieval_col_stats): for every gallery row j, over all
+    queries, (col_max fp32 [Ng] = max_i T * s[i][j],  col_sum fp32 [Ng] = sum_i exp(T * s[i][j] - col_max[j])), s the
+    scores retrieval_rank compares.  query fp32 [Nq, D], gallery fp32 [Ng, D], T a float >= 0.  Inference only."""
+    _need_gpu(query, gallery)
+    if query.dtype != torch.float32 or gallery.dtype != torch.float32:
+        raise TypeError(f'retrieval_col_stats takes fp32 embeddings (got {query.dtype}, {gallery.dtype})')
+    if query.dim() != 2 or gallery.dim() != 2 or query.shape[1] != gallery.shape[1]:
+        raise ValueError(f'retrieval_col_stats: query [Nq, D] and gallery [Ng, D] (got {tuple(query.shape)}, '
+                         f'{tuple(gallery.shape)})')
+    q, g = query.detach(), gallery.detach()
+    q = q if q.stride(1) == 1 or q.shape[1] == 1 else q.contiguous()
+    g = g if g.stride(1) == 1 or g.shape[1] == 1 else g.contiguous()
+    Nq, D = q.shape
+    Ng = g.shape[0]
+    L = _lib.lib()
+    nbytes = L.clv_retrieval_col_stats_work_bytes(Nq, Ng, D)
+    check(min(nbytes, 0), 'clv_retrieval_col_stats_work_bytes')
+    work = torch.empty(nbytes, device=q.device, dtype=torch.uint8)
+    cmax = torch.empty(Ng, device=q.device, dtype=torch.float32)
+    csum = torch.empty(Ng, device=q.device, dtype=torch.float32)
+    check(L.clv_retrieval_col_stats(_ptr(q), _ptr(g), Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), float(T),
+                                    _ptr(cmax), _ptr(csum), _ptr(work), _stream()), 'clv_retrieval_col_stats')
+    return cmax, csum
 
 
 def retrieval_group_best(query, gallery, lo=None, hi=None, want_rank=False, eps=0.0):

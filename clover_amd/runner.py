@@ -314,7 +314,10 @@ class EvalHook(Hook):
     also collects the labels — zero-shot multiple choice, ``ops.retrieval_group_best`` —, with
     ``'recall_for_video_text_retrieval_varied'`` it is ``multi_gpu_test_retrieval_varied``); ``'use_itm_head_fn'`` ->
     ``multi_gpu_test_itm_finetune`` + ``evaluate_qa``; a callable ``test_fn(model, dataloader)`` returns the metrics dict
-    itself.  EVERY rank runs the test loop (its collection is a collective); rank 0 alone evaluates, appends
+    itself.  ``dual_softmax = T`` (``evaluation = dict(..., dual_softmax=T)``) adds the ``DSL_*`` keys of the two recall
+    metrics — ranks under the dual-softmax prior, ``ops.retrieval_rank(..., dual_softmax=T)`` — next to the plain ones
+    (``save_best='DSL_Recall@1'`` follows the ``Recall@`` rule); multiple choice and video QA refuse it.
+    EVERY rank runs the test loop (its collection is a collective); rank 0 alone evaluates, appends
     ``dict(epoch, **metrics)`` to ``records``, prints it through ``printer`` (what ``LogHook`` is given) and saves.
     The best score and path live in ``runner.meta['hook_msgs']`` (``best_score``, ``best_ckpt``), which checkpoints carry
     and ``CloverRunner.resume`` restores; the best checkpoint is ``{basename(work_dir)}_best_{key}_epoch_{n}.pth`` and
@@ -334,7 +337,7 @@ class EvalHook(Hook):
 
     def __init__(self, dataloader, start=None, interval=1, by_epoch=True, save_best='auto', rule=None, test_fn=None,
                  greater_keys=None, less_keys=None, gpu_collect=True, metrics=None, broadcast_bn_buffer=True,
-                 printer=None):
+                 printer=None, dual_softmax=None):
         if interval <= 0:
             raise ValueError(f'interval must be a positive number, but got {interval}')
         assert isinstance(by_epoch, bool), '``by_epoch`` should be a boolean'
@@ -350,6 +353,12 @@ class EvalHook(Hook):
         if metrics is None:
             metrics = ['video_qa_mc'] if test_fn == 'use_itm_head_fn' else ['recall_for_video_text_retrieval']
         self.metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+        self.dual_softmax = None if dual_softmax is None else float(dual_softmax)
+        if self.dual_softmax is not None and (callable(test_fn) or test_fn == 'use_itm_head_fn' or
+                                              'video_qa_mc' in self.metrics):
+            from .evaluation.retrieval import _NO_DSL_MC
+            raise ValueError(_NO_DSL_MC if not callable(test_fn) else
+                             'dual_softmax: a callable test_fn computes its own metrics')
         self.gpu_collect, self.broadcast_bn_buffer, self.printer = gpu_collect, broadcast_bn_buffer, printer
         as_list = lambda k, d: list(d) if k is None else ([k] if isinstance(k, str) else list(k))          # noqa: E731
         self.greater_keys = as_list(greater_keys, self._default_greater_keys)
@@ -457,7 +466,10 @@ class EvalHook(Hook):
         else:
             res = multi_gpu_test_retrieval(model, self.dataloader, gpu_collect=self.gpu_collect, to_host=False,
                                            with_label='video_qa_mc' in self.metrics)
-        return evaluate_retrieval(res, self.metrics) if rank == 0 else None
+        if rank != 0:
+            return None
+        opt = {} if self.dual_softmax is None else dict(dual_softmax=self.dual_softmax)
+        return evaluate_retrieval(res, self.metrics, **opt)
 
     def _do_evaluate(self, runner):
         rank, world = self._rank_world()

@@ -912,6 +912,33 @@ int clv_retrieval_group_best(const float* query, const float* gallery, const int
                              int32_t* best_idx, float* best_score, int32_t* rank, void* work, int64_t Nq, int64_t Ng,
                              int32_t D, int64_t ldq, int64_t ldg, float eps, void* stream);
 
+/* Dual-softmax re-scoring of text -> video retrieval at inference: s'[i][j] = s[i][j] * softmax_i(T s[i][j]), the softmax
+ * taken down the QUERY axis (a gallery row that scores high for every query is damped for all of them).  Two entries, no
+ * [Nq][Ng] matrix; query / gallery / normalisation / s[i][j] as clv_retrieval_rank (bit-equal scores).
+ *
+ * clv_retrieval_col_stats: for every gallery row j, over ALL Nq queries,
+ *   col_max[j] = m_j = max_i T s[i][j]            col_sum[j] = l_j = sum_i exp(T s[i][j] - m_j)        (float [Ng] each)
+ * A workgroup owns 64 gallery rows and walks the queries with an online max / sum; a long query set is split over
+ * workgroups whose partials are joined in chunk order (no float atomics): results are deterministic.  T = 0 gives
+ * m_j = 0 and l_j = Nq exactly (Nq <= 2^24).
+ *
+ * clv_retrieval_rank_prior: clv_retrieval_rank's outputs and rules (rank, gt_score, topk_idx / topk_score, stable
+ * descending order, ties by index, -1 / NaN where gt is out of range) on the compared value
+ *   s'[i][j] = s[i][j] * exp(T s[i][j] - col_max[j]) / col_sum[j]                (fp32, one rounding per operation)
+ * with col_max / col_sum as clv_retrieval_col_stats wrote them for the same operands and T; gt_score and topk_score are s'.
+ *
+ * work: clv_retrieval_col_stats_work_bytes(...) / clv_retrieval_rank_prior_work_bytes(...) bytes, 16-byte aligned (the two
+ * calls may share one area of the larger size); nothing is allocated inside, every launch goes to `stream` (capturable).
+ * Shape limits and error codes of clv_retrieval_rank; T finite and >= 0 (T s must stay finite), else CLV_ERR_ARG. */
+int64_t clv_retrieval_col_stats_work_bytes(int64_t Nq, int64_t Ng, int32_t D);
+int clv_retrieval_col_stats(const float* query, const float* gallery, int64_t Nq, int64_t Ng, int32_t D, int64_t ldq,
+                            int64_t ldg, float T, float* col_max, float* col_sum, void* work, void* stream);
+int64_t clv_retrieval_rank_prior_work_bytes(int64_t Nq, int64_t Ng, int32_t D, int32_t topk);
+int clv_retrieval_rank_prior(const float* query, const float* gallery, const int32_t* gt, int32_t* rank, float* gt_score,
+                             int32_t* topk_idx, float* topk_score, void* work, int64_t Nq, int64_t Ng, int32_t D,
+                             int64_t ldq, int64_t ldg, int32_t topk, const float* col_max, const float* col_sum, float T,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@ reference's finetune_msrvtt_mc.py; ``synthetic_test.candidates = C`` captions pe
 video, ``--v2t`` adds the video -> text keys) run the same two encoders; their scores stay on the device
 (ops.retrieval_group_best) and ``--out`` holds the chosen candidate per video as ``pred``.
 
+Dual-softmax re-scoring (``--dual-softmax T``, or ``evaluation = dict(..., dual_softmax=T)`` in the config as
+configs/finetune_retrieval_dsl_synthetic.py): the two recall metrics print ``DSL_Recall@K`` / ``DSL_MR`` next to the plain
+keys (the prior runs over all queries of the test set), and with ``--topk K --out`` the file also holds ``dsl_topk``.
+
 Video QA / fill-in-the-blank (a config with ``evaluation.test_fn='use_itm_head_fn'``, or ``--eval video_qa_mc`` /
 ``video_qa_oe``): ``forward_test`` scores every sample (multi_gpu_test_itm_finetune, my_eval_hook.py:317-380) and rank 0
 prints ``acc`` / ``overall_acc`` (video_dataset.py:304-343) over ``data.synthetic_test`` = dict(pairs, frames, tokens,
@@ -44,6 +48,9 @@ def parse_args():
                    help='retrieval only: score on the device and add the K best video indices per query to --out (1..16)')
     p.add_argument('--v2t', action='store_true',
                    help='recall_for_video_text_retrieval_varied only: add V2T_Recall@K / V2T_MR (best caption per video)')
+    p.add_argument('--dual-softmax', type=float, default=None, metavar='T',
+                   help='retrieval recall only: add the DSL_* keys, ranks under s * softmax(T * s) over all queries '
+                        '(default: evaluation.dual_softmax of the config)')
     p.add_argument('--cfg-options', nargs='+', default=[], help='a.b=c overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none', help='job launcher')
     return p.parse_args()
@@ -88,6 +95,9 @@ def main():
     varied = kind == 'retrieval' and 'recall_for_video_text_retrieval_varied' in metrics
     if args.v2t and not varied:
         raise SystemExit('--v2t: with recall_for_video_text_retrieval_varied only')
+    dsl = args.dual_softmax if args.dual_softmax is not None else (cfg.get('evaluation') or {}).get('dual_softmax')
+    if dsl is not None and (kind != 'retrieval' or mc or args.v2t):
+        raise SystemExit('--dual-softmax: the two retrieval recall metrics only (not multiple choice, video QA or --v2t)')
     if not torch.cuda.is_available():
         raise SystemExit('tools/test.py needs an MI355X (no CPU fallback)')
     if args.launcher == 'none':
@@ -125,16 +135,20 @@ def main():
         results = multi_gpu_test_retrieval(model, loader, to_host=not on_device, with_label=mc)
     if rank == 0:
         if on_device:                                     # ranks, the K best videos per query, the chosen candidates
-            metrics = evaluate_retrieval(results, metrics, topk=args.topk, with_pred=mc, v2t=args.v2t)
+            metrics = evaluate_retrieval(results, metrics, topk=args.topk, with_pred=mc, v2t=args.v2t, dual_softmax=dsl)
+        elif kind == 'qa':
+            metrics = evaluate_qa(results, metrics)
         else:
-            metrics = (evaluate_qa if kind == 'qa' else evaluate_retrieval)(results, metrics)
-        topk, pred = metrics.pop('topk', None), metrics.pop('pred', None)
+            metrics = evaluate_retrieval(results, metrics, dual_softmax=dsl)
+        topk, pred, dsl_topk = metrics.pop('topk', None), metrics.pop('pred', None), metrics.pop('dsl_topk', None)
         for k, v in metrics.items():
             print(f'{k}: {v:.04f}')                                                   # tools/test.py:255-256
         if args.out:
             out = dict(metrics={k: float(v) for k, v in metrics.items()}, pairs=int(len(results['index'])))
             if topk is not None:
                 out['topk'] = topk.tolist()
+            if dsl_topk is not None:
+                out['dsl_topk'] = dsl_topk.tolist()
             if pred is not None:
                 out['pred'] = pred.tolist()
             with open(args.out, 'w') as f:
