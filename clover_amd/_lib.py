@@ -102,6 +102,24 @@ class ClvMlpFusedPlan(C.Structure):
     _fields_ = [(n, _i32) for n in ('grid', 'tiles_min', 'tiles_max', 'trips', 'half_group')]
 
 
+class ClvLossGemmPlan(C.Structure):
+    """Mirror of ``struct ClvLossGemmPlan`` (include/clover_hip.h): the kernel one GEMM of the loss section takes."""
+    _fields_ = [(n, _i32) for n in ('kernel', 'waves', 'gx', 'gy', 'tiles', 'kchunk', 'waves_with_work', 'k_tail')]
+
+
+class ClvFocalPlan(C.Structure):
+    """Mirror of ``struct ClvFocalPlan`` (include/clover_hip.h): the focal kernels a row layout takes."""
+    _fields_ = [(n, _i32) for n in ('fwd_kernel', 'bwd_kernel', 'fwd_threads', 'bwd_threads', 'fwd_trips',
+                                    'fwd_waves_with_work')]
+
+
+class ClvLossPlan(C.Structure):
+    """Mirror of ``struct ClvLossPlan`` (include/clover_hip.h): the launches of an InfoNCE / NormSoftmax evaluation."""
+    _fields_ = [(n, ClvLossGemmPlan) for n in ('fwd', 'bwd0', 'bwd1')] + [(n, _i32) for n in (
+        'large', 'loss_threads', 'loss_trips', 'rows_grid', 'cols_gx', 'cols_gy', 'finish_threads', 'cols_last',
+        'idle_row_lanes', 'idle_col_waves')]
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),
@@ -175,6 +193,10 @@ SIGNATURES = {
     'clv_infonce_pair_bwd_large': (C.c_int, [_p] * 4 + [_i32, _i32, _i32, _f, _f, _p]),
     'clv_normsoftmax_fwd_large': (C.c_int, [_p] * 5 + [_i32, _i32, _f, _f, _p]),
     'clv_normsoftmax_bwd_large': (C.c_int, [_p] * 6 + [_i32, _i32, _f, _p]),
+    'clv_loss_gemm_plan': (C.c_int, [_i32] * 6 + [_i64] * 3 + [_i32] * 3 + [C.POINTER(ClvLossGemmPlan)]),
+    'clv_focal_plan': (C.c_int, [_i32, _i32, _i64, _i32, _i32, C.POINTER(ClvFocalPlan)]),
+    'clv_infonce_plan': (C.c_int, [_i32] * 5 + [C.POINTER(ClvLossPlan)]),
+    'clv_normsoftmax_plan': (C.c_int, [_i32] * 4 + [C.POINTER(ClvLossPlan)]),
     'clv_sumsq': (C.c_int, [_p, _p, _i64, _p]),
     'clv_adamw_step': (C.c_int, [_p] * 6 + [_i64] + [_f] * 9 + [_p]),
     'clv_gemm_nt_supported': (C.c_int, [_i64, _i32, _i32]),

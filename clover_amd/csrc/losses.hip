@@ -184,19 +184,42 @@ struct NceWork {
 __host__ __device__ inline int64_t nce_work_floats(int G, int Dm) {
     return (int64_t)4 * G * Dm * 3 + (int64_t)4 * G + (int64_t)3 * G * G * 3 + (int64_t)6 * G + 16 + (int64_t)6 * G;
 }
+// Offsets (floats) of the parts of a work area with nb score blocks (InfoNCE: 3, NormSoftmax: 1), in the order of the
+// layout comments: the carves below and the plan entries (which need the operand addresses modulo 16 only) both read them.
+struct LossWorkOff {
+    int64_t en, enT, den, invn, sim, dsim, dsimT, lser, lsec, acc, term;
+};
+__host__ __device__ inline LossWorkOff loss_work_off(int nb, int G, int Dm) {
+    const int64_t emb = (int64_t)(nb + 1) * G * Dm, blk = (int64_t)nb * G * G;
+    LossWorkOff o;
+    int64_t w = 0;
+    o.en = w; w += emb;
+    o.enT = w; w += emb;
+    o.den = w; w += emb;
+    o.invn = w; w += (nb + 1) * G;
+    o.sim = w; w += blk;
+    o.dsim = w; w += blk;
+    o.dsimT = w; w += blk;
+    o.lser = w; w += nb * G;
+    o.lsec = w; w += nb * G;
+    o.acc = w; w += 16;
+    o.term = w;
+    return o;
+}
 __host__ __device__ inline NceWork nce_carve(float* w, int G, int Dm) {
+    const LossWorkOff o = loss_work_off(3, G, Dm);
     NceWork W;
-    W.en = w; w += (int64_t)4 * G * Dm;
-    W.enT = w; w += (int64_t)4 * G * Dm;
-    W.den = w; w += (int64_t)4 * G * Dm;
-    W.invn = w; w += 4 * G;
-    W.sim = w; w += (int64_t)3 * G * G;
-    W.dsim = w; w += (int64_t)3 * G * G;
-    W.dsimT = w; w += (int64_t)3 * G * G;
-    W.lser = w; w += 3 * G;
-    W.lsec = w; w += 3 * G;
-    W.acc = w; w += 16;
-    W.term = w;
+    W.en = w + o.en;
+    W.enT = w + o.enT;
+    W.den = w + o.den;
+    W.invn = w + o.invn;
+    W.sim = w + o.sim;
+    W.dsim = w + o.dsim;
+    W.dsimT = w + o.dsimT;
+    W.lser = w + o.lser;
+    W.lsec = w + o.lsec;
+    W.acc = w + o.acc;
+    W.term = w + o.term;
     return W;
 }
 
@@ -243,6 +266,10 @@ __global__ void __launch_bounds__(256) nce_pair_normalize_kernel(NcePair P, int 
 // K multiple of 16 is NOT required (tail guarded); rows/cols guarded.  NW waves split the contraction (partial tiles meet in
 // LDS): the similarity GEMMs have G x G outputs — a handful of tiles — and Dm = 768 to contract: one wave per tile walked 48
 // dependent load rounds (20 us); the gradient GEMMs contract over <= 3 G and keep one wave.
+__host__ __device__ inline int sgemm_kchunk(int K, int nw) {      // per wave, a multiple of 16 (clv_loss_gemm_plan reports it)
+    return ((K + nw * 16 - 1) / (nw * 16)) * 16;
+}
+
 template <int NW>
 __global__ void __launch_bounds__(64 * NW) sgemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                       float* __restrict__ C, int M, int N, int K, int lda, int ldb,
@@ -260,7 +287,7 @@ __global__ void __launch_bounds__(64 * NW) sgemm_nt_kernel(const float* __restri
     const float* ap = A + (int64_t)(i < M ? i : 0) * lda;
     const float* bp = B + (int64_t)(j < N ? j : 0) * ldb;
     const bool av = i < M, bv = j < N;
-    const int kchunk = ((K + NW * 16 - 1) / (NW * 16)) * 16;       // per wave, a multiple of 16
+    const int kchunk = sgemm_kchunk(K, NW);
     const int kb = wave * kchunk, ke = min(K, kb + kchunk);
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     for (int k0 = kb; k0 < ke; k0 += 16) {
@@ -459,17 +486,18 @@ __host__ __device__ inline int64_t ns_work_floats(int G, int Dm) {
     return (int64_t)2 * G * Dm * 3 + (int64_t)2 * G + (int64_t)G * G * 3 + (int64_t)2 * G + 16 + (int64_t)2 * G;
 }
 __host__ __device__ inline NsWork ns_carve(float* w, int G, int Dm) {
+    const LossWorkOff o = loss_work_off(1, G, Dm);
     NsWork W;
-    W.en = w; w += (int64_t)2 * G * Dm;
-    W.enT = w; w += (int64_t)2 * G * Dm;
-    W.den = w; w += (int64_t)2 * G * Dm;
-    W.invn = w; w += 2 * G;
-    W.sim = w; w += (int64_t)G * G;
-    W.dsim = w; w += (int64_t)G * G;
-    W.dsimT = w; w += (int64_t)G * G;
-    W.lser = w; w += G;
-    W.lsec = w; w += G + 16;
-    W.term = w;
+    W.en = w + o.en;
+    W.enT = w + o.enT;
+    W.den = w + o.den;
+    W.invn = w + o.invn;
+    W.sim = w + o.sim;
+    W.dsim = w + o.dsim;
+    W.dsimT = w + o.dsimT;
+    W.lser = w + o.lser;
+    W.lsec = w + o.lsec;
+    W.term = w + o.term;
     return W;
 }
 
@@ -746,16 +774,38 @@ __global__ void __launch_bounds__(256) sgemm_nt_tiled_kernel(const float* __rest
 
 }  // namespace
 
+// Which focal kernels serve a row layout: the launches below and clv_focal_plan read the same record.
+static void focal_plan(bool is16, int V, int64_t ld, uintptr_t logits_addr, uintptr_t dlogits_addr, ClvFocalPlan& p) {
+    const bool even = is16 && !(V & 1) && !(ld & 1);
+    p.fwd_kernel = !is16 ? 0 : (even && !(logits_addr & 3)) ? 2 : 1;
+    p.bwd_kernel = !is16 ? 0 : (even && !((logits_addr | dlogits_addr) & 3)) ? 2 : 1;
+    p.fwd_threads = p.fwd_kernel == 2 ? FC_WIDE : FC_THREADS;
+    p.bwd_threads = p.bwd_kernel == 2 ? FC_WIDE : FC_THREADS;
+    const int n = p.fwd_kernel == 2 ? V >> 1 : V;                      // accesses per row
+    p.fwd_trips = (n + p.fwd_threads - 1) / p.fwd_threads;
+    const int waves = p.fwd_threads / 64, busy = (n + 63) / 64;
+    p.fwd_waves_with_work = busy < waves ? busy : waves;
+}
+
+extern "C" int clv_focal_plan(int32_t is_16bit, int32_t V, int64_t ld, int32_t logits_align, int32_t dlogits_align,
+                              ClvFocalPlan* out) {
+    if (!out || V <= 0 || ld < V || logits_align < 0 || dlogits_align < 0) return CLV_ERR_ARG;
+    focal_plan(is_16bit != 0, V, ld, (uintptr_t)logits_align, (uintptr_t)dlogits_align, *out);
+    return 0;
+}
+
 static int focal_fwd_impl(const void* logits, int32_t is_bf16, const int64_t* labels, float* row_ce, float* row_lse,
                           float* loss, float* count, int64_t rows, int32_t V, int64_t ld, float gamma, void* stream) {
     if (!logits || !labels || !row_ce || !row_lse || !loss || !count || rows <= 0 || V <= 0 || ld < V) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
+    ClvFocalPlan pl;
+    focal_plan(is_bf16 != 0, V, ld, reinterpret_cast<uintptr_t>(logits), 0, pl);
     // (loss, count) double as the {sum, count} accumulators (caller zeroes both); normalised in place
     // by the finish kernel
-    if (is_bf16 && !(V & 1) && !(ld & 1) && !(reinterpret_cast<uintptr_t>(logits) & 3))
+    if (pl.fwd_kernel == 2)
         hipLaunchKernelGGL(focal_fwd_pairs_kernel, dim3((unsigned)rows), dim3(FC_WIDE), 0, st, (const unsigned*)logits,
                            labels, row_ce, row_lse, loss, count, (int)V, ld, gamma);
-    else if (is_bf16)
+    else if (pl.fwd_kernel == 1)
         hipLaunchKernelGGL((focal_fwd_kernel<true>), dim3((unsigned)rows), dim3(FC_THREADS), 0, st, logits, labels,
                            row_ce, row_lse, loss, count, (int)V, ld, gamma);
     else
@@ -773,11 +823,12 @@ static int focal_bwd_impl(const void* logits, int32_t is_bf16, const int64_t* la
     if (!logits || !labels || !row_ce || !row_lse || !count || !dloss || !dlogits || rows <= 0 || V <= 0 || ld < V)
         return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (is_bf16 && !(V & 1) && !(ld & 1) &&
-        !((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(dlogits)) & 3))
+    ClvFocalPlan pl;
+    focal_plan(is_bf16 != 0, V, ld, reinterpret_cast<uintptr_t>(logits), reinterpret_cast<uintptr_t>(dlogits), pl);
+    if (pl.bwd_kernel == 2)
         hipLaunchKernelGGL(focal_bwd_pairs_kernel, dim3((unsigned)rows), dim3(FC_WIDE), 0, st, (const unsigned*)logits,
                            labels, row_ce, row_lse, count, dloss, (unsigned*)dlogits, (int)V, ld, gamma);
-    else if (is_bf16)
+    else if (pl.bwd_kernel == 1)
         hipLaunchKernelGGL((focal_bwd_kernel<true>), dim3((unsigned)rows), dim3(FC_THREADS), 0, st, logits, labels,
                            row_ce, row_lse, count, dloss, dlogits, (int)V, ld, gamma);
     else
@@ -829,29 +880,133 @@ static int nce_loss_threads(int G) {
 // of the eager form lies between 64 and 128: the threshold is the smallest size measured at which both forms are ahead.
 constexpr int NCE_LARGE_MIN_G = 128;
 
+// Which kernel a GEMM of the loss section takes: nce_gemm launches by this record and clv_loss_gemm_plan returns it.
+static void loss_gemm_plan(int M, int N, int K, int lda, int ldb, int batch, int64_t sA, int64_t sB, int64_t s2,
+                           uintptr_t a_addr, uintptr_t b_addr, bool tiled, ClvLossGemmPlan& p) {
+    p.k_tail = K % 16;
+    if (tiled) {
+        p.gx = (N + LT_BN - 1) / LT_BN;
+        p.gy = (M + LT_BM - 1) / LT_BM;
+        const bool vec = K % LT_BK == 0 && lda % 4 == 0 && ldb % 4 == 0 && sA % 4 == 0 && sB % 4 == 0 && s2 % 4 == 0 &&
+                         a_addr % 16 == 0 && b_addr % 16 == 0;
+        p.kernel = vec ? 2 : 3;
+        p.waves = p.waves_with_work = 4;
+        p.kchunk = LT_BK;
+    } else {
+        p.gx = (N + 15) / 16;
+        p.gy = (M + 15) / 16;
+        // few tiles (per evaluation), long contraction: 8 waves share a tile
+        const bool wide = K >= 256 && (int64_t)p.gx * p.gy * batch <= 512;
+        p.kernel = wide ? 1 : 0;
+        p.waves = wide ? 8 : 1;
+        p.kchunk = sgemm_kchunk(K, p.waves);
+        const int busy = (K + p.kchunk - 1) / p.kchunk;
+        p.waves_with_work = busy < p.waves ? busy : p.waves;
+    }
+    p.tiles = (int32_t)((int64_t)p.gx * p.gy * batch);
+}
+
+extern "C" int clv_loss_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t batch, int64_t sA,
+                                  int64_t sB, int64_t s2, int32_t a_align, int32_t b_align, int32_t tiled,
+                                  ClvLossGemmPlan* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldb < K || batch <= 0 || a_align < 0 || b_align < 0)
+        return CLV_ERR_ARG;
+    loss_gemm_plan(M, N, K, lda, ldb, batch, sA, sB, s2, (uintptr_t)a_align, (uintptr_t)b_align, tiled != 0, *out);
+    return 0;
+}
+
 static int nce_gemm(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                     int batch, int64_t sA, int64_t sB, int64_t sC, float alpha, hipStream_t st, int outer = 1,
                     int64_t s2 = 0, bool tiled = false) {
-    if (tiled) {
-        const dim3 tgrid((N + LT_BN - 1) / LT_BN, (M + LT_BM - 1) / LT_BM, batch * outer);
-        const bool vec = K % LT_BK == 0 && lda % 4 == 0 && ldb % 4 == 0 && sA % 4 == 0 && sB % 4 == 0 && s2 % 4 == 0 &&
-                         reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0;
-        if (vec)
-            hipLaunchKernelGGL(sgemm_nt_tiled_kernel<true>, tgrid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
-                               sC, alpha, batch, s2);
-        else
-            hipLaunchKernelGGL(sgemm_nt_tiled_kernel<false>, tgrid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
-                               sC, alpha, batch, s2);
-        return clv_check_launch();
-    }
-    const dim3 grid((N + 15) / 16, (M + 15) / 16, batch * outer);
-    if (K >= 256 && (int64_t)grid.x * grid.y * batch <= 512)       // few tiles (per evaluation), long contraction: 8 waves share a tile
+    ClvLossGemmPlan pl;
+    loss_gemm_plan(M, N, K, lda, ldb, batch, sA, sB, s2, reinterpret_cast<uintptr_t>(A), reinterpret_cast<uintptr_t>(B),
+                   tiled, pl);
+    const dim3 grid(pl.gx, pl.gy, batch * outer);
+    if (pl.kernel == 2)
+        hipLaunchKernelGGL(sgemm_nt_tiled_kernel<true>, grid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
+                           sC, alpha, batch, s2);
+    else if (pl.kernel == 3)
+        hipLaunchKernelGGL(sgemm_nt_tiled_kernel<false>, grid, dim3(256), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB,
+                           sC, alpha, batch, s2);
+    else if (pl.kernel == 1)
         hipLaunchKernelGGL(sgemm_nt_kernel<8>, grid, dim3(512), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, alpha,
                            batch, s2);
     else
         hipLaunchKernelGGL(sgemm_nt_kernel<1>, grid, dim3(64), 0, st, A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, alpha,
                            batch, s2);
     return clv_check_launch();
+}
+
+// The three GEMMs of an evaluation on a carved work area (NceWork: nb = 3 score blocks; NsWork: nb = 1).  which: 0 the
+// scores en0 . en_{k+1}^T, 1 d en0 = dsim . en_{1..nb} (contraction nb * G), 2 d en_{k+1} = dsimT[k] . en0 (contraction G).
+// The launches and the plan entries both come through here.
+struct LossGemmArgs {
+    int64_t oA, oB, oC;                        // operand offsets (floats) from the start of the work area
+    int M, N, K, lda, ldb, ldc, batch;
+    int64_t sA, sB, sC;
+};
+static LossGemmArgs loss_gemm_args(int which, int nb, int G, int Dm) {
+    const LossWorkOff o = loss_work_off(nb, G, Dm);
+    const int64_t GD = (int64_t)G * Dm, GG = (int64_t)G * G;
+    const bool many = nb > 1;
+    if (which == 0) return {o.en, o.en + GD, o.sim, G, G, Dm, Dm, Dm, G, nb, 0, many ? GD : 0, many ? GG : 0};
+    // d en0[i][d] = sum_{k,j} dsim[i][(k,j)] * en_{k+1}[j][d] / T :  A = dsim [G][nb G], B = enT[d][(k+1, j)]
+    if (which == 1) return {o.dsim, o.enT + G, o.den, G, Dm, nb * G, nb * G, (nb + 1) * G, Dm, 1, 0, 0, 0};
+    // d en_{k+1}[j][d] = sum_i dsimT[k][j][i] * en0[i][d] / T   :  A = dsimT[k] [G][G], B = enT[d][(0, i)]
+    return {o.dsimT, o.enT, o.den + GD, G, Dm, G, G, (nb + 1) * G, Dm, nb, many ? GG : 0, 0, many ? GD : 0};
+}
+template <class WK>
+static int loss_gemm(const WK& W, int which, int nb, int G, int Dm, float alpha, hipStream_t st, int outer, int64_t s2,
+                     bool tiled) {
+    const LossGemmArgs a = loss_gemm_args(which, nb, G, Dm);
+    float* work = W.en;                        // the work area starts with en
+    return nce_gemm(work + a.oA, work + a.oB, work + a.oC, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.batch, a.sA, a.sB, a.sC,
+                    alpha, st, outer, s2, tiled);
+}
+
+// Launch shapes of the loss kernels between the GEMMs; the forwards below launch by this record.
+static void loss_kernels_plan(int G, int nb, bool large, ClvLossPlan& p) {
+    p.large = large;
+    p.loss_threads = p.loss_trips = p.rows_grid = p.cols_gx = p.cols_gy = p.finish_threads = p.cols_last = 0;
+    p.idle_row_lanes = p.idle_col_waves = 0;
+    if (!large) {
+        p.loss_threads = nb == 3 ? nce_loss_threads(G) : 1024;
+        p.loss_trips = (2 * nb * G + p.loss_threads - 1) / p.loss_threads;
+        return;
+    }
+    p.rows_grid = (nb * G + 3) / 4;
+    p.cols_gx = (G + 63) / 64;
+    p.cols_gy = nb;
+    p.finish_threads = 256;
+    p.cols_last = G - 64 * (p.cols_gx - 1);
+    p.idle_row_lanes = G < 64 ? 64 - G : 0;
+    p.idle_col_waves = G < LSE_COL_WAVES ? LSE_COL_WAVES - G : 0;
+}
+
+// For a work area at a 16-byte boundary: operand addresses modulo 16 follow from the offsets.
+static void loss_section_plan(int nb, int G, int Dm, int64_t s2, bool large, bool gemms, ClvLossPlan& p) {
+    loss_kernels_plan(G, nb, large, p);
+    ClvLossGemmPlan* g[3] = {&p.fwd, &p.bwd0, &p.bwd1};
+    for (int which = 0; which < 3; ++which) {
+        *g[which] = ClvLossGemmPlan{};
+        if (!gemms) continue;
+        const LossGemmArgs a = loss_gemm_args(which, nb, G, Dm);
+        loss_gemm_plan(a.M, a.N, a.K, a.lda, a.ldb, a.batch, a.sA, a.sB, s2, (uintptr_t)(a.oA * 4), (uintptr_t)(a.oB * 4),
+                       large, *g[which]);
+    }
+}
+
+// ld is checked as the entry checks it; no launch class depends on it
+extern "C" int clv_infonce_plan(int32_t G, int32_t Dm, int32_t ld, int32_t pair, int32_t large, ClvLossPlan* out) {
+    if (!out || G <= 0 || Dm <= 0 || ld < Dm) return CLV_ERR_ARG;
+    loss_section_plan(3, G, Dm, pair ? nce_work_floats(G, Dm) : 0, large != 0, true, *out);
+    return 0;
+}
+
+extern "C" int clv_normsoftmax_plan(int32_t G, int32_t Dm, int32_t sim_mat, int32_t large, ClvLossPlan* out) {
+    if (!out || G <= 0 || (!sim_mat && Dm <= 0)) return CLV_ERR_ARG;
+    loss_section_plan(1, G, Dm > 0 ? Dm : 1, 0, large != 0, !sim_mat, *out);
+    return 0;
 }
 
 static int infonce_fwd_impl(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
@@ -866,18 +1021,19 @@ static int infonce_fwd_impl(const float* e0, const float* e1, const float* e2, c
     int rc = clv_check_launch();
     if (rc) return rc;
     // sim[k] = en0 . en_{k+1}^T / temperature
-    rc = nce_gemm(W.en, W.en + (int64_t)G * Dm, W.sim, G, G, Dm, Dm, Dm, G, 3, 0, (int64_t)G * Dm, (int64_t)G * G,
-                  1.0f / temperature, st, 1, 0, large);
+    rc = loss_gemm(W, 0, 3, G, Dm, 1.0f / temperature, st, 1, 0, large);
     if (rc) return rc;
+    ClvLossPlan pl;
+    loss_kernels_plan(G, 3, large, pl);
     if (!large) {
-        hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(nce_loss_threads(G)), 0, st, W, out, (int)G, margin);
+        hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(pl.loss_threads), 0, st, W, out, (int)G, margin);
         return clv_check_launch();
     }
-    hipLaunchKernelGGL(nce_lse_rows_kernel, dim3((3 * G + 3) / 4), dim3(256), 0, st, W, (int)G);
+    hipLaunchKernelGGL(nce_lse_rows_kernel, dim3(pl.rows_grid), dim3(256), 0, st, W, (int)G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_lse_cols_kernel, dim3((G + 63) / 64, 3), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G);
+    hipLaunchKernelGGL(nce_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_finish_kernel, dim3(1), dim3(256), 0, st, W, out, (int)G, margin);
+    hipLaunchKernelGGL(nce_finish_kernel, dim3(1), dim3(pl.finish_threads), 0, st, W, out, (int)G, margin);
     return clv_check_launch();
 }
 
@@ -906,12 +1062,9 @@ static int infonce_bwd_impl(const float* dout, const float* work, float* d0, flo
     int rc = clv_check_launch();
     if (rc) return rc;
     const float it = 1.0f / temperature;
-    // d en0[i][d] = sum_{k,j} dsim[i][(k,j)] * en_{k+1}[j][d] / T :  A = dsim [G][3G], B = enT[d][(k+1, j)]
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
+    rc = loss_gemm(W, 1, 3, G, Dm, it, st, 1, 0, large);
     if (rc) return rc;
-    // d en_{k+1}[j][d] = sum_i dsimT[k][j][i] * en0[i][d] / T   :  A = dsimT[k] [G][G], B = enT[d][(0, i)]
-    rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 4 * G, Dm, 3, (int64_t)G * G, 0,
-                  (int64_t)G * Dm, it, st, 1, 0, large);
+    rc = loss_gemm(W, 2, 3, G, Dm, it, st, 1, 0, large);
     if (rc) return rc;
     hipLaunchKernelGGL(nce_norm_bwd_kernel, dim3((4 * G + 3) / 4), dim3(256), 0, st, W, d0, d1, d2, d3, (int)G, (int)Dm,
                        (int)ldd);
@@ -957,18 +1110,20 @@ static int infonce_pair_fwd_impl(const float* packed, const int32_t* slots, floa
                        (int)(k * Dm));
     int rc = clv_check_launch();
     if (rc) return rc;
-    rc = nce_gemm(P.w[0].en, P.w[0].en + (int64_t)G * Dm, P.w[0].sim, G, G, Dm, Dm, Dm, G, 3, 0, (int64_t)G * Dm,
-                  (int64_t)G * G, 1.0f / temperature, st, 2, ws, large);
+    rc = loss_gemm(P.w[0], 0, 3, G, Dm, 1.0f / temperature, st, 2, ws, large);
     if (rc) return rc;
+    ClvLossPlan pl;
+    loss_kernels_plan(G, 3, large, pl);
     if (!large) {
-        hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(2), dim3(nce_loss_threads(G)), 0, st, P, out, (int)G, margin);
+        hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(2), dim3(pl.loss_threads), 0, st, P, out, (int)G, margin);
         return clv_check_launch();
     }
-    hipLaunchKernelGGL(nce_pair_lse_rows_kernel, dim3((3 * G + 3) / 4, 2), dim3(256), 0, st, P, (int)G);
+    hipLaunchKernelGGL(nce_pair_lse_rows_kernel, dim3(pl.rows_grid, 2), dim3(256), 0, st, P, (int)G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_pair_lse_cols_kernel, dim3((G + 63) / 64, 3, 2), dim3(64 * LSE_COL_WAVES), 0, st, P, (int)G);
+    hipLaunchKernelGGL(nce_pair_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy, 2), dim3(64 * LSE_COL_WAVES), 0, st, P,
+                       (int)G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_pair_finish_kernel, dim3(2), dim3(256), 0, st, P, out, (int)G, margin);
+    hipLaunchKernelGGL(nce_pair_finish_kernel, dim3(2), dim3(pl.finish_threads), 0, st, P, out, (int)G, margin);
     return clv_check_launch();
 }
 
@@ -998,10 +1153,9 @@ static int infonce_pair_bwd_impl(const float* const* dout, const float* work, co
     if (rc) return rc;
     const float it = 1.0f / temperature;
     const NceWork& W = P.w[0];
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, 3 * G, 3 * G, 4 * G, Dm, 1, 0, 0, 0, it, st, 2, ws, large);
+    rc = loss_gemm(W, 1, 3, G, Dm, it, st, 2, ws, large);
     if (rc) return rc;
-    rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 4 * G, Dm, 3, (int64_t)G * G, 0,
-                  (int64_t)G * Dm, it, st, 2, ws, large);
+    rc = loss_gemm(W, 2, 3, G, Dm, it, st, 2, ws, large);
     if (rc) return rc;
     hipLaunchKernelGGL(nce_pair_norm_bwd_kernel, dim3((k * G + 3) / 4), dim3(256), 0, st, P, dpacked, (int)G, (int)k,
                        (int)Dm);
@@ -1032,21 +1186,22 @@ static int normsoftmax_fwd_impl(const float* video, const float* text, const flo
                            eps);
         int rc = clv_check_launch();
         if (rc) return rc;
-        rc = nce_gemm(W.en, W.en + (int64_t)G * Dm, W.sim, G, G, Dm, Dm, Dm, G, 1, 0, 0, 0, 1.0f / temperature, st, 1, 0,
-                      large);
+        rc = loss_gemm(W, 0, 1, G, Dm, 1.0f / temperature, st, 1, 0, large);
         if (rc) return rc;
     }
     const float* sim = sim_mat ? sim_mat : (const float*)W.sim;
+    ClvLossPlan pl;
+    loss_kernels_plan(G, 1, large, pl);
     if (!large) {
-        hipLaunchKernelGGL(ns_loss_kernel, dim3(1), dim3(1024), 0, st, W, sim, out, (int)G);
+        hipLaunchKernelGGL(ns_loss_kernel, dim3(1), dim3(pl.loss_threads), 0, st, W, sim, out, (int)G);
         return clv_check_launch();
     }
-    hipLaunchKernelGGL(ns_lse_rows_kernel, dim3((G + 3) / 4), dim3(256), 0, st, W, sim, (int)G);
+    hipLaunchKernelGGL(ns_lse_rows_kernel, dim3(pl.rows_grid), dim3(256), 0, st, W, sim, (int)G);
     int rc = clv_check_launch();
     if (rc) return rc;
-    hipLaunchKernelGGL(ns_lse_cols_kernel, dim3((G + 63) / 64, 1), dim3(64 * LSE_COL_WAVES), 0, st, W, sim, (int)G);
+    hipLaunchKernelGGL(ns_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), dim3(64 * LSE_COL_WAVES), 0, st, W, sim, (int)G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(ns_finish_kernel, dim3(1), dim3(256), 0, st, W, out, (int)G);
+    hipLaunchKernelGGL(ns_finish_kernel, dim3(1), dim3(pl.finish_threads), 0, st, W, out, (int)G);
     return clv_check_launch();
 }
 
@@ -1075,9 +1230,9 @@ static int normsoftmax_bwd_impl(const float* sim_mat, const float* dout, const f
     if (rc || sim_mat) return rc;
     const float it = 1.0f / temperature;
     // d en_v[i][d] = sum_j dsim[i][j] en_t[j][d] / t ;  d en_t[j][d] = sum_i dsim[i][j] en_v[i][d] / t
-    rc = nce_gemm(W.dsim, W.enT + G, W.den, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
+    rc = loss_gemm(W, 1, 1, G, Dm, it, st, 1, 0, large);
     if (rc) return rc;
-    rc = nce_gemm(W.dsimT, W.enT, W.den + (int64_t)G * Dm, G, Dm, G, G, 2 * G, Dm, 1, 0, 0, 0, it, st, 1, 0, large);
+    rc = loss_gemm(W, 2, 1, G, Dm, it, st, 1, 0, large);
     if (rc) return rc;
     hipLaunchKernelGGL(ns_norm_bwd_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, W, dvideo, dtext, (int)G, (int)Dm);
     return clv_check_launch();

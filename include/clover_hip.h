@@ -538,6 +538,58 @@ int clv_normsoftmax_fwd_large(const float* video, const float* text, const float
 int clv_normsoftmax_bwd_large(const float* sim_mat, const float* dout, const float* work, float* dvideo, float* dtext,
                               float* dsim, int32_t G, int32_t Dm, float temperature, void* stream);
 
+/* What the loss entries above launch (host only, no GPU needed; four symbols added to ABI 20 — new symbols, nothing existing
+ * changes, the version stays).  The launch code decides on the same records, so the entries cannot drift from it.  Each
+ * returns CLV_ERR_ARG where the entry it describes would (and for out == NULL).
+ *
+ * clv_loss_gemm_plan: one fp32 GEMM of the loss section, C = alpha A[M][K] . B[N][K]^T, `batch` of them per evaluation with
+ * operand strides sA, sB and s2 floats between the two evaluations of the pair form (0 without).  a_align / b_align: the base
+ * addresses of A and B modulo 16 (bytes); tiled: 1 on the *_large entries.
+ *   kernel           0 one wave per 16 x 16 tile; 1 eight waves split the contraction of a tile (K >= 256 and at most 512
+ *                    tiles per evaluation); 2 LDS tiles 64 x 64 x 16 staged with 16-byte loads; 3 the same staged element by
+ *                    element with row and contraction guards (K % 16 != 0, a stride that is no multiple of 4 floats, or a
+ *                    base address off a 16-byte boundary)
+ *   waves            per workgroup (1, 8, 4);  gx, gy: tiles across N and M;  tiles = gx * gy * batch
+ *   kchunk           contraction elements per wave (kernels 0, 1: a multiple of 16) or per LDS stage (16)
+ *   waves_with_work  waves whose first element wave * kchunk lies below K (kernel 1 with K < 7 kchunk + 1: the rest idle)
+ *   k_tail           K % 16: elements of the last, guarded 16-step (0: none) */
+typedef struct ClvLossGemmPlan {
+    int32_t kernel, waves, gx, gy, tiles, kchunk, waves_with_work, k_tail;
+} ClvLossGemmPlan;
+int clv_loss_gemm_plan(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t batch, int64_t sA, int64_t sB,
+                       int64_t s2, int32_t a_align, int32_t b_align, int32_t tiled, ClvLossGemmPlan* out);
+/* clv_focal_plan: clv_focal_ce_fwd(_ld) / _bwd(_ld) for rows of V scores with stride ld.  logits_align / dlogits_align: the
+ * base addresses modulo 4 (bytes).  The forward looks at logits alone, the backward at both.
+ *   fwd_kernel, bwd_kernel  0 fp32, 256 threads; 1 16-bit, one 2-byte element per access, 256 threads; 2 16-bit PAIRS (one
+ *                           4-byte access), 1024 threads: V and ld even and the base addresses on 4-byte boundaries
+ *   fwd_threads, bwd_threads
+ *   fwd_trips               accesses of the busiest thread over a row (2-byte / fp32: per pass); >= 2 on the pair kernel: a
+ *                           thread rescales its own running sum
+ *   fwd_waves_with_work     waves of the forward workgroup that own at least one element */
+typedef struct ClvFocalPlan {
+    int32_t fwd_kernel, bwd_kernel, fwd_threads, bwd_threads, fwd_trips, fwd_waves_with_work;
+} ClvFocalPlan;
+int clv_focal_plan(int32_t is_16bit, int32_t V, int64_t ld, int32_t logits_align, int32_t dlogits_align, ClvFocalPlan* out);
+/* clv_infonce_plan / clv_normsoftmax_plan: one evaluation (pair: 1 = the pair entries, whose second work area starts
+ * clv_infonce_work_floats(G, Dm) floats after the first) on a work buffer at a 16-byte boundary.  large: 0 the entries
+ * without suffix, 1 the *_large entries.  sim_mat: 1 = NormSoftmaxLoss on a given score matrix (no GEMM runs: the three GEMM
+ * records are zero).  ld is checked as clv_infonce_fwd checks it; no launch class depends on it.
+ *   fwd, bwd0, bwd1  the score GEMM(s); d en of the first operand (K = 3 G, NormSoftmax: G); d en of the others (K = G)
+ *   loss_threads, loss_trips   large == 0: the one-workgroup loss kernel and the exclusive rows / columns its busiest thread
+ *                              walks (6 G of them, NormSoftmax: 2 G)
+ *   rows_grid, cols_gx, cols_gy, finish_threads   large == 1: workgroups of the row kernel (4 rows each), of the column
+ *                              kernel (64 columns x one score block each), threads of the finish kernel
+ *   cols_last         columns of the last column group (< 64: ragged)
+ *   idle_row_lanes    lanes of a row's wave without an element (G < 64);  idle_col_waves: the same for the 16 waves of a
+ *                     column group (G < 16) */
+typedef struct ClvLossPlan {
+    ClvLossGemmPlan fwd, bwd0, bwd1;
+    int32_t large, loss_threads, loss_trips, rows_grid, cols_gx, cols_gy, finish_threads, cols_last, idle_row_lanes,
+        idle_col_waves;
+} ClvLossPlan;
+int clv_infonce_plan(int32_t G, int32_t Dm, int32_t ld, int32_t pair, int32_t large, ClvLossPlan* out);
+int clv_normsoftmax_plan(int32_t G, int32_t Dm, int32_t sim_mat, int32_t large, ClvLossPlan* out);
+
 /* ------------------------------------------------------------------ optimizer
  * Grad-norm (clip_grad_norm_, mmcv_Fp16OptimizerHook.py:127-137) + AdamW step on flat
  * buffers (optimizer cfg pretrain_webvid_cc3m.py:129-137).

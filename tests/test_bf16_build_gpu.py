@@ -23,7 +23,8 @@ def _run(args):
 @pytest.mark.skipif(os.environ.get('CLOVER_HALF', 'f16').lower() == 'bf16', reason='this process already runs the bf16 build')
 def test_kernels_in_the_bf16_build():
     out = _run(['tests/test_kernels_gpu.py', 'tests/test_attention_gpu.py', 'tests/test_norm_act_gpu.py',
-                'tests/test_wgrad_gpu.py', 'tests/test_gemm_nt_gpu.py', 'tests/test_mlp_gpu.py', '--deselect',
+                'tests/test_wgrad_gpu.py', 'tests/test_gemm_nt_gpu.py', 'tests/test_mlp_gpu.py', 'tests/test_losses_gpu.py',
+                '--deselect',
                 'tests/test_kernels_gpu.py::test_grouped_weight_gradients_shape_fitted_tiles'])
     assert ' passed' in out
 

@@ -44,13 +44,13 @@ def close(got, ref):
 
 @functools.lru_cache(maxsize=None)
 def case(G, Dm):
-    """packed fp32 [G, 6, Dm] (positives correlated, so that the ranking hinge is active for some rows only) and the fp64
-    oracle on it: the four losses of the two evaluations and the gradient of their WTS-weighted sum.  Computed once."""
-    g = torch.Generator().manual_seed(1000 + G + Dm)
-    p = torch.randn(G, 6, Dm, generator=g)
-    p[:, 1] = p[:, 0] * 0.7 + p[:, 1] * 0.5
-    p[:, 2] = p[:, 0] * 0.6 + p[:, 2] * 0.6
-    p[:, 4] = p[:, 1] * 0.6 + p[:, 4] * 0.6
+    """packed fp32 [G, 6, Dm] (loss_ref.nce_packed: positives correlated and every third masked row flipped, so that the
+    ranking hinge of both evaluations is active on some rows and inactive on others — asserted) and the fp64 oracle on it:
+    the four losses of the two evaluations and the gradient of their WTS-weighted sum.  Computed once."""
+    import loss_ref
+    p = loss_ref.nce_packed(G, Dm)
+    for s3 in (SA[:3], SB[:3]):
+        loss_ref.assert_mixed_hinge(*[p[:, s] for s in s3])
     pr = p.double().requires_grad_()
     la = om.exclusive_nce_rank_loss(*[pr[:, s] for s in SA], temperature=0.05, margin=5.0, gather=False)
     lb = om.exclusive_nce_rank_loss(*[pr[:, s] for s in SB], temperature=0.05, margin=5.0, gather=False)

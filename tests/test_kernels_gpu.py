@@ -362,10 +362,10 @@ def test_focal_ce(dtype, V):
 @pytest.mark.parametrize('G', [1, 2, 8, 64, 200])
 def test_infonce(G):
     Dm = 768 if G > 2 else 128
-    es = [rnd(G, Dm, seed=50 + k) for k in range(4)]
-    # make positives close so that the ranking hinge is active for some rows and not others
-    es[1] = es[0] * 0.7 + es[1] * 0.5
-    es[2] = es[0] * 0.6 + es[2] * 0.6
+    import loss_ref
+    packed = loss_ref.nce_packed(G, Dm, seed=50 + G)      # positives close, every third masked-text row flipped
+    es = [packed[:, k].clone() for k in range(4)]
+    loss_ref.assert_mixed_hinge(*es[:3])                  # the ranking hinge is active on some rows and inactive on others
     er = [e.clone().requires_grad_() for e in es]
     l = om.exclusive_nce_rank_loss(*er, temperature=0.05, margin=5.0, gather=False)
     (l['nce_loss'] * 1.3 + l['rank_t_tm_loss'] * 0.7).backward()
@@ -407,10 +407,11 @@ def test_infonce_pair_equals_two_packed_evaluations(G):
     one evaluation reads, to rounding (the two contributions are summed before the normalisation's Jacobian instead of after)
     on the two slots both read; a slot nobody reads gets zeros.  Distinct upstream gradients per loss."""
     Dm, k = 768, 7
-    packed = rnd(G, k, Dm, seed=181)
-    packed[:, 1] = packed[:, 0] * 0.7 + packed[:, 1] * 0.5
-    packed[:, 4] = packed[:, 1] * 0.6 + packed[:, 4] * 0.6
+    import loss_ref
+    packed = loss_ref.mixed_hinge_(rnd(G, k, Dm, seed=181))
     sa, sb = (0, 1, 2, 3), (1, 0, 4, 5)
+    for s3 in (sa[:3], sb[:3]):                           # both branches of the hinge run in both evaluations
+        loss_ref.assert_mixed_hinge(*[packed[:, s_] for s_ in s3])
     wts = (1.3, 0.7, 0.9, 1.1)
     pg = packed.to(DEV).requires_grad_()
     outs = ops().exclusive_infonce_rank_pair(pg, sa, sb, 0.05, 5.0)
