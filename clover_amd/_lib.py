@@ -197,6 +197,12 @@ SIGNATURES = {
     'clv_focal_plan': (C.c_int, [_i32, _i32, _i64, _i32, _i32, C.POINTER(ClvFocalPlan)]),
     'clv_infonce_plan': (C.c_int, [_i32] * 5 + [C.POINTER(ClvLossPlan)]),
     'clv_normsoftmax_plan': (C.c_int, [_i32] * 4 + [C.POINTER(ClvLossPlan)]),
+    'clv_dsl_loss_work_floats': (C.c_int64, [_i32, _i32]),
+    'clv_dsl_loss_fwd': (C.c_int, [_p] * 4 + [_i32, _i32, _f, _f, _f, _p]),
+    'clv_dsl_loss_bwd': (C.c_int, [_p] * 4 + [_i32, _i32, _f, _f, _p]),
+    'clv_dsl_loss_fwd_large': (C.c_int, [_p] * 4 + [_i32, _i32, _f, _f, _f, _p]),
+    'clv_dsl_loss_bwd_large': (C.c_int, [_p] * 4 + [_i32, _i32, _f, _f, _p]),
+    'clv_dsl_loss_plan': (C.c_int, [_i32] * 3 + [C.POINTER(ClvLossPlan)]),
     'clv_sumsq': (C.c_int, [_p, _p, _i64, _p]),
     'clv_adamw_step': (C.c_int, [_p] * 6 + [_i64] + [_f] * 9 + [_p]),
     'clv_gemm_nt_supported': (C.c_int, [_i64, _i32, _i32]),

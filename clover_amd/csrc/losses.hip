@@ -772,6 +772,236 @@ __global__ void __launch_bounds__(256) sgemm_nt_tiled_kernel(const float* __rest
         }
 }
 
+// =========================================================================== dual-softmax loss (DSL)
+// NormSoftmaxLoss under the dual-softmax prior (the training half of retrieval.hip's re-scoring; not in the reference).  With
+// c = en_v . en_t^T (the cosine, held in `sim`: the score GEMM runs with alpha 1), x = T c and a = G / temperature:
+//   Pr = softmax over i of x      yr = (a c) Pr     (video -> text logits; its log-sum-exp runs along a row)
+//   Pc = softmax over j of x      yc = (a c) Pc     (text -> video logits; its log-sum-exp runs down a column)
+//   loss = -(sum_i (yr[i][i] - lse_j yr[i][j]) + sum_j (yc[j][j] - lse_i yc[i][j])) / G
+// Every exponential takes an argument that a maximum or a log-sum-exp of its own row / column was subtracted from, so T = 100
+// (most priors underflow to 0) stays finite.  y is formed on the fly from c and the prior statistics: no second G x G matrix.
+// Backward, with gr = softmax_j(yr) - [i == j], gc = softmax_i(yc) - [i == j] (the 1 / G is folded into the scale):
+//   u[j] = sum_i (gr c) Pr      w[i] = sum_j (gc c) Pc
+//   d loss / d c = dout / temperature * ( Pr (gr (1 + x) - T u[j]) + Pc (gc (1 + x) - T w[i]) )
+// work layout: that of NormSoftmax (NsWork; lser / lsec hold the log-sums of yr / yc), then the prior statistics
+// pc.m, pc.l, pr.m, pr.l, the maxima yr.m, yc.m, and w, u: [G] each.  The backward reads only what the forward
+// left there, and both forms leave the same numbers in the same places: either backward accepts either forward's work.
+// The arithmetic of this section is written with contraction off, one rounding per operation, so that tests/dsl_loss_ref.py
+// can repeat it (lse_push keeps its fused multiply-add, as loss_ref models it).
+// A log-sum-exp kept in two parts: the maximum m and l = log sum exp(. - m).  exp((v - m) - l) then rounds differences of
+// order 1, where exp(v - (m + l)) would carry the rounding of a sum of the logits' magnitude (G / temperature at worst)
+// into every probability of the row.
+struct DslStat {
+    float *m, *l;
+};
+struct DslWork {
+    NsWork ns;
+    DslStat pc, pr, yr, yc;          // of x per row i / per column j; of yr per row i / of yc per column j
+    float *w, *u;
+};
+__host__ __device__ inline int64_t dsl_work_floats(int G, int Dm) { return ns_work_floats(G, Dm) + (int64_t)8 * G; }
+__host__ __device__ inline DslWork dsl_carve(float* w, int G, int Dm) {
+    DslWork W;
+    W.ns = ns_carve(w, G, Dm);
+    float* x = w + ns_work_floats(G, Dm);
+    const int64_t g = G;
+    W.pc = {x, x + g};
+    W.pr = {x + 2 * g, x + 3 * g};
+    W.yr = {x + 4 * g, W.ns.lser};
+    W.yc = {x + 5 * g, W.ns.lsec};
+    W.w = x + 6 * g;
+    W.u = x + 7 * g;
+    return W;
+}
+
+// l = log(s), correctly rounded (the fp64 logarithm rounded once): 4 G of them per evaluation.  A last-bit difference of a
+// prior's l moves every logit of its column by a c P 2^-24 l, hundreds of ulps of a probability at a = G / temperature, so
+// the hardware's 1-ulp log2 is not used here (tests/DSL_LOSS_ERROR_BUDGET.md, "the logarithm").
+__device__ __forceinline__ float dsl_log(float s) { return (float)log((double)s); }
+__device__ __forceinline__ float dsl_x(float c, float T) {
+#pragma clang fp contract(off)
+    return T * c;
+}
+// exp((v - m) - l): a prior from x, a probability from y
+__device__ __forceinline__ float dsl_p(float v, float m, float l) {
+#pragma clang fp contract(off)
+    return __expf((v - m) - l);
+}
+// the logit of one entry: (pm, pl) is the prior statistic of the entry's column (yr) or row (yc)
+__device__ __forceinline__ float dsl_y(float c, float T, float a, float pm, float pl) {
+#pragma clang fp contract(off)
+    return (a * c) * dsl_p(T * c, pm, pl);
+}
+// gr c Pr (prior of column j, statistic of yr's row i) or gc c Pc (prior of row i, statistic of yc's column j) of one entry
+__device__ __forceinline__ float dsl_gcp(float c, bool diag, float T, float a, float pm, float pl, float ym, float yl) {
+#pragma clang fp contract(off)
+    const float p = dsl_p(T * c, pm, pl);
+    const float g = dsl_p((a * c) * p, ym, yl) - (diag ? 1.f : 0.f);
+    return (g * c) * p;
+}
+
+// single block: G row + G column prior statistics (one thread each), then G row + G column log-sum-exps of y, then the loss.
+__global__ void __launch_bounds__(1024) dsl_loss_kernel(DslWork W, float* __restrict__ out, int G, float T, float a) {
+#pragma clang fp contract(off)
+    __shared__ float sh[16];
+    const float* c = W.ns.sim;
+    for (int t = threadIdx.x; t < 2 * G; t += blockDim.x) {
+        const bool col = t >= G;
+        const int u = col ? t - G : t;
+        const int64_t base = col ? u : (int64_t)u * G, step = col ? G : 1;
+        float m = -INFINITY;
+        for (int j = 0; j < G; ++j) m = fmaxf(m, dsl_x(c[base + j * step], T));
+        float s = 0.f;
+        for (int j = 0; j < G; ++j) s += __expf(dsl_x(c[base + j * step], T) - m);
+        const DslStat& st = col ? W.pr : W.pc;
+        st.m[u] = m;
+        st.l[u] = dsl_log(s);
+    }
+    __syncthreads();                                          // the statistics of the other axis are read below
+    float part = 0.f;
+    for (int t = threadIdx.x; t < 2 * G; t += blockDim.x) {
+        const bool col = t >= G;
+        const int u = col ? t - G : t;
+        const int64_t base = col ? u : (int64_t)u * G, step = col ? G : 1;
+        const DslStat& p = col ? W.pc : W.pr;                 // a row walks columns j: pr[j]; a column walks rows i: pc[i]
+        float m = -INFINITY;
+        for (int j = 0; j < G; ++j) m = fmaxf(m, dsl_y(c[base + j * step], T, a, p.m[j], p.l[j]));
+        float s = 0.f;
+        for (int j = 0; j < G; ++j) s += __expf(dsl_y(c[base + j * step], T, a, p.m[j], p.l[j]) - m);
+        const float l = dsl_log(s);
+        const DslStat& st = col ? W.yc : W.yr;
+        st.m[u] = m;
+        st.l[u] = l;
+        part += (dsl_y(c[(int64_t)u * G + u], T, a, p.m[u], p.l[u]) - m) - l;
+    }
+    const float tot = block_reduce(part, sh, false);
+    if (threadIdx.x == 0) out[0] = -(tot / (float)G);
+}
+
+// The multi-workgroup forward: lse_rows_body / lse_cols_body with the value formed on the fly.  YPASS false: the prior
+// statistics of x = T c; true: the log-sum-exp of y and the term (diag - m) - l for ns_finish_kernel.
+template <bool YPASS>
+__global__ void __launch_bounds__(256) dsl_rows_kernel(DslWork W, int G, float T, float a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= G) return;
+    const float* row = W.ns.sim + (int64_t)i * G;
+    float m = -INFINITY, s = 0.f;
+    for (int j = lane; j < G; j += 64) lse_push(m, s, YPASS ? dsl_y(row[j], T, a, W.pr.m[j], W.pr.l[j]) : dsl_x(row[j], T));
+    const float wm = wave_max(m);
+    s = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - wm));  // a lane without elements (G < 64)
+    if (lane == 0) {
+        const float l = dsl_log(s);
+        const DslStat& st = YPASS ? W.yr : W.pc;
+        st.m[i] = wm;
+        st.l[i] = l;
+        if (YPASS) W.ns.term[i] = (dsl_y(row[i], T, a, W.pr.m[i], W.pr.l[i]) - wm) - l;
+    }
+}
+
+template <bool YPASS>
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) dsl_cols_kernel(DslWork W, int G, float T, float a) {
+#pragma clang fp contract(off)
+    __shared__ float shm[LSE_COL_WAVES][64], shs[LSE_COL_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + lane;
+    const float* c = W.ns.sim;
+    float m = -INFINITY, s = 0.f;
+    if (j < G)
+        for (int i = wv; i < G; i += LSE_COL_WAVES) {
+            const float v = c[(int64_t)i * G + j];
+            lse_push(m, s, YPASS ? dsl_y(v, T, a, W.pc.m[i], W.pc.l[i]) : dsl_x(v, T));
+        }
+    shm[wv][lane] = m;
+    shs[wv][lane] = s;
+    __syncthreads();
+    if (wv != 0 || j >= G) return;
+    float bm = shm[0][lane];
+#pragma unroll
+    for (int w = 1; w < LSE_COL_WAVES; ++w) bm = fmaxf(bm, shm[w][lane]);
+    float bs = 0.f;
+#pragma unroll
+    for (int w = 0; w < LSE_COL_WAVES; ++w)
+        if (shm[w][lane] != -INFINITY) bs = __builtin_fmaf(shs[w][lane], __expf(shm[w][lane] - bm), bs);
+    const float l = dsl_log(bs);
+    const DslStat& st = YPASS ? W.yc : W.pr;
+    st.m[j] = bm;
+    st.l[j] = l;
+    if (YPASS) W.ns.term[G + j] = (dsl_y(c[(int64_t)j * G + j], T, a, W.pc.m[j], W.pc.l[j]) - bm) - l;
+}
+
+// backward reductions, one-workgroup form's order: one thread per row (w) / column (u) adds its G terms one after the other
+__global__ void __launch_bounds__(64) dsl_uw_kernel(DslWork W, int G, float T, float a) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= 2 * G) return;
+    const float* c = W.ns.sim;
+    const bool col = t >= G;
+    const int u = col ? t - G : t;
+    const int64_t base = col ? u : (int64_t)u * G, step = col ? G : 1;
+    const DslStat& p = col ? W.pr : W.pc;                     // u[j]: Pr of column j, yr of row i;  w[i]: Pc of row i, yc of column j
+    const DslStat& y = col ? W.yr : W.yc;
+    const float pm = p.m[u], pl = p.l[u];
+    float s = 0.f;
+    for (int k = 0; k < G; ++k) s += dsl_gcp(c[base + k * step], k == u, T, a, pm, pl, y.m[k], y.l[k]);
+    (col ? W.u : W.w)[u] = s;
+}
+
+// the same at a global batch: one wave per row, lanes stride the columns, wave_sum
+__global__ void __launch_bounds__(256) dsl_w_rows_kernel(DslWork W, int G, float T, float a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= G) return;
+    const float* row = W.ns.sim + (int64_t)i * G;
+    const float pm = W.pc.m[i], pl = W.pc.l[i];
+    float s = 0.f;
+    for (int j = lane; j < G; j += 64) s += dsl_gcp(row[j], j == i, T, a, pm, pl, W.yc.m[j], W.yc.l[j]);
+    s = wave_sum(s);
+    if (lane == 0) W.w[i] = s;
+}
+
+// 64 adjacent columns per workgroup, 16 waves share the rows, the 16 partial sums of a column meet in LDS in wave order
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) dsl_u_cols_kernel(DslWork W, int G, float T, float a) {
+#pragma clang fp contract(off)
+    __shared__ float shs[LSE_COL_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j = blockIdx.x * 64 + lane;
+    float s = 0.f;
+    if (j < G) {
+        const float pm = W.pr.m[j], pl = W.pr.l[j];
+        for (int i = wv; i < G; i += LSE_COL_WAVES)
+            s += dsl_gcp(W.ns.sim[(int64_t)i * G + j], i == j, T, a, pm, pl, W.yr.m[i], W.yr.l[i]);
+    }
+    shs[wv][lane] = s;
+    __syncthreads();
+    if (wv != 0 || j >= G) return;
+    float bs = 0.f;
+#pragma unroll
+    for (int w = 0; w < LSE_COL_WAVES; ++w) bs += shs[w][lane];
+    W.u[j] = bs;
+}
+
+// elementwise: d loss / d c, and its transpose for the second gradient GEMM
+__global__ void __launch_bounds__(256) dsl_dsim_kernel(DslWork W, const float* __restrict__ dout, int G, float T, float a,
+                                                       float invt) {
+#pragma clang fp contract(off)
+    const int64_t total = (int64_t)G * G;
+    const float scale = dout[0] * invt;                       // dout a / G
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int i = (int)(idx / G), j = (int)(idx - (int64_t)i * G);
+        const float c = W.ns.sim[idx], dg = i == j ? 1.f : 0.f;
+        const float x = T * c, ac = a * c;
+        const float pr = dsl_p(x, W.pr.m[j], W.pr.l[j]), pc = dsl_p(x, W.pc.m[i], W.pc.l[i]);
+        const float gr = dsl_p(ac * pr, W.yr.m[i], W.yr.l[i]) - dg, gc = dsl_p(ac * pc, W.yc.m[j], W.yc.l[j]) - dg;
+        const float k = 1.f + x;
+        const float d = scale * (pr * (gr * k - T * W.u[j]) + pc * (gc * k - T * W.w[i]));
+        W.ns.dsim[idx] = d;
+        W.ns.dsimT[(int64_t)j * G + i] = d;
+    }
+}
+
 }  // namespace
 
 // Which focal kernels serve a row layout: the launches below and clv_focal_plan read the same record.
@@ -1247,4 +1477,98 @@ extern "C" int clv_normsoftmax_bwd_large(const float* sim_mat, const float* dout
                                          float* dtext, float* dsim, int32_t G, int32_t Dm, float temperature,
                                          void* stream) {
     return normsoftmax_bwd_impl(sim_mat, dout, work, dvideo, dtext, dsim, G, Dm, temperature, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------------- dual-softmax loss
+extern "C" int64_t clv_dsl_loss_work_floats(int32_t G, int32_t Dm) { return dsl_work_floats(G, Dm > 0 ? Dm : 1); }
+
+// The launch shapes and the three GEMM classes are those of NormSoftmax on embeddings: the same record.
+extern "C" int clv_dsl_loss_plan(int32_t G, int32_t Dm, int32_t large, ClvLossPlan* out) {
+    if (!out || G <= 0 || Dm <= 0) return CLV_ERR_ARG;
+    loss_section_plan(1, G, Dm, 0, large != 0, true, *out);
+    return 0;
+}
+
+static bool dsl_prior_ok(float T) { return T >= 0.f && T <= 3.4e38f; }      // false for NaN and inf
+
+static int dsl_fwd_impl(const float* video, const float* text, float* out, float* work, int32_t G, int32_t Dm,
+                        float temperature, float eps, float T, void* stream, bool large) {
+    if (!video || !text || !out || !work || G <= 0 || Dm <= 0 || temperature <= 0.f || eps <= 0.f || !dsl_prior_ok(T))
+        return CLV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    DslWork W = dsl_carve(work, G, Dm);
+    hipLaunchKernelGGL(ns_normalize_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, video, text, W.ns, (int)G, (int)Dm, eps);
+    int rc = clv_check_launch();
+    if (rc) return rc;
+    rc = loss_gemm(W.ns, 0, 1, G, Dm, 1.0f, st, 1, 0, large);             // the cosine: 1 / temperature is folded into a
+    if (rc) return rc;
+    const float a = (float)G / temperature;
+    ClvLossPlan pl;
+    loss_kernels_plan(G, 1, large, pl);
+    if (!large) {
+        hipLaunchKernelGGL(dsl_loss_kernel, dim3(1), dim3(pl.loss_threads), 0, st, W, out, (int)G, T, a);
+        return clv_check_launch();
+    }
+    const dim3 cols(pl.cols_gx, pl.cols_gy), colt(64 * LSE_COL_WAVES);
+    hipLaunchKernelGGL(dsl_rows_kernel<false>, dim3(pl.rows_grid), dim3(256), 0, st, W, (int)G, T, a);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(dsl_cols_kernel<false>, cols, colt, 0, st, W, (int)G, T, a);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(dsl_rows_kernel<true>, dim3(pl.rows_grid), dim3(256), 0, st, W, (int)G, T, a);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(dsl_cols_kernel<true>, cols, colt, 0, st, W, (int)G, T, a);
+    if ((rc = clv_check_launch())) return rc;
+    hipLaunchKernelGGL(ns_finish_kernel, dim3(1), dim3(pl.finish_threads), 0, st, W.ns, out, (int)G);
+    return clv_check_launch();
+}
+
+extern "C" int clv_dsl_loss_fwd(const float* video, const float* text, float* out, float* work, int32_t G, int32_t Dm,
+                                float temperature, float eps, float dual_softmax, void* stream) {
+    return dsl_fwd_impl(video, text, out, work, G, Dm, temperature, eps, dual_softmax, stream, false);
+}
+extern "C" int clv_dsl_loss_fwd_large(const float* video, const float* text, float* out, float* work, int32_t G,
+                                      int32_t Dm, float temperature, float eps, float dual_softmax, void* stream) {
+    return dsl_fwd_impl(video, text, out, work, G, Dm, temperature, eps, dual_softmax, stream, true);
+}
+
+static int dsl_bwd_impl(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G, int32_t Dm,
+                        float temperature, float T, void* stream, bool large) {
+    if (!dout || !work || !dvideo || !dtext || G <= 0 || Dm <= 0 || temperature <= 0.f || !dsl_prior_ok(T))
+        return CLV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    DslWork W = dsl_carve(const_cast<float*>(work), G, Dm);
+    const float a = (float)G / temperature;
+    ClvLossPlan pl;
+    loss_kernels_plan(G, 1, large, pl);
+    int rc;
+    if (!large) {
+        hipLaunchKernelGGL(dsl_uw_kernel, dim3((2 * G + 63) / 64), dim3(64), 0, st, W, (int)G, T, a);
+        if ((rc = clv_check_launch())) return rc;
+    } else {
+        hipLaunchKernelGGL(dsl_w_rows_kernel, dim3(pl.rows_grid), dim3(256), 0, st, W, (int)G, T, a);
+        if ((rc = clv_check_launch())) return rc;
+        hipLaunchKernelGGL(dsl_u_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G, T, a);
+        if ((rc = clv_check_launch())) return rc;
+    }
+    const int64_t total = (int64_t)G * G;
+    int grid = (int)((total + 255) / 256);
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(dsl_dsim_kernel, dim3(grid), dim3(256), 0, st, W, dout, (int)G, T, a, 1.0f / temperature);
+    if ((rc = clv_check_launch())) return rc;
+    // d en_v[i][d] = sum_j dc[i][j] en_t[j][d] ;  d en_t[j][d] = sum_i dc[i][j] en_v[i][d]
+    rc = loss_gemm(W.ns, 1, 1, G, Dm, 1.0f, st, 1, 0, large);
+    if (rc) return rc;
+    rc = loss_gemm(W.ns, 2, 1, G, Dm, 1.0f, st, 1, 0, large);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ns_norm_bwd_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, W.ns, dvideo, dtext, (int)G, (int)Dm);
+    return clv_check_launch();
+}
+
+extern "C" int clv_dsl_loss_bwd(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G, int32_t Dm,
+                                float temperature, float dual_softmax, void* stream) {
+    return dsl_bwd_impl(dout, work, dvideo, dtext, G, Dm, temperature, dual_softmax, stream, false);
+}
+extern "C" int clv_dsl_loss_bwd_large(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G,
+                                      int32_t Dm, float temperature, float dual_softmax, void* stream) {
+    return dsl_bwd_impl(dout, work, dvideo, dtext, G, Dm, temperature, dual_softmax, stream, true);
 }

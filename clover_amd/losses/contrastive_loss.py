@@ -62,12 +62,18 @@ class NormSoftmaxLoss(nn.Module):
     """The retrieval fine-tuning loss (mmaction/models/losses/contrastive_loss.py:26-68): all-gather video / text
     embeddings (``GatherLoss``: the backward keeps the local slice only), normalise, similarity / temperature,
     -mean diag(log_softmax) in both directions.  The arithmetic after the gather is the fused HIP path
-    ``clv_normsoftmax_fwd/bwd``."""
+    ``clv_normsoftmax_fwd/bwd``.
 
-    def __init__(self, temperature=0.07, cos_sim=False):
+    ``dual_softmax = T`` (not in the reference; ``None`` = the plain loss, unchanged) trains with the dual-softmax prior
+    that ``evaluation = dict(..., dual_softmax=T)`` scores with: logits (G / temperature) c softmax(T c) in both directions
+    (``clv_dsl_loss_fwd/bwd``).  Gather, local-slice backward and ``equal_batch`` are those of the plain loss; a given
+    ``sim_mat`` is refused."""
+
+    def __init__(self, temperature=0.07, cos_sim=False, dual_softmax=None):
         super().__init__()
         self.t = temperature
         self.use_cos_similarity = cos_sim
+        self.dual_softmax = None if dual_softmax is None else ops.dual_softmax_temperature(dual_softmax)
         self.fp16_enabled = False
         self.equal_batch = True                  # GatherLoss (:42-43) requires equal per-rank batches
 
@@ -81,7 +87,8 @@ class NormSoftmaxLoss(nn.Module):
 
     def forward(self, video_embd=None, text_embd=None, sim_mat=None):
         if sim_mat is not None:                  # :55-56
-            return ops.norm_softmax_loss(sim_mat=sim_mat)
+            return ops.norm_softmax_loss(sim_mat=sim_mat, dual_softmax=self.dual_softmax)
         v, t = packed_all_gather([video_embd, text_embd], equal_sizes=self.equal_batch)
         # F.normalize clamps the norm at 1e-12 (:51-52); the cos_sim variant (sim_matrix :10-18) at 1e-8
-        return ops.norm_softmax_loss(v, t, temperature=self.t, eps=1e-8 if self.use_cos_similarity else 1e-12)
+        return ops.norm_softmax_loss(v, t, temperature=self.t, eps=1e-8 if self.use_cos_similarity else 1e-12,
+                                     dual_softmax=self.dual_softmax)

@@ -2499,9 +2499,60 @@ class _NormSoftmax(torch.autograd.Function):
         return dv.to(dts[0]), dt.to(dts[1]), None, None, None
 
 
-def norm_softmax_loss(video=None, text=None, sim_mat=None, temperature=0.07, eps=1e-12):
-    """NormSoftmaxLoss (contrastive_loss.py:26-68) on already-gathered [G,Dm] embeddings or a [G,G] sim_mat."""
-    return _NormSoftmax.apply(video, text, sim_mat, temperature, eps)
+class _DualSoftmaxLoss(torch.autograd.Function):
+    """NormSoftmaxLoss under the dual-softmax prior (csrc/losses.hip clv_dsl_loss_*): dtype handling as _NormSoftmax."""
+
+    @staticmethod
+    def forward(ctx, video, text, temperature, eps, T):
+        L = _lib.lib()
+        _need_gpu(video, text)
+        v, t = _c(video.float()), _c(text.float())
+        if v.dim() != 2 or t.shape != v.shape:
+            raise ValueError(f'NormSoftmaxLoss: video {tuple(v.shape)} vs text {tuple(t.shape)}')
+        G, Dm = v.shape
+        work = torch.empty(L.clv_dsl_loss_work_floats(G, Dm), device=v.device, dtype=torch.float32)
+        out = torch.empty(1, device=v.device, dtype=torch.float32)
+        fwd, ctx.large = _nce_fn('clv_dsl_loss_fwd', G)
+        check(fwd(_ptr(v), _ptr(t), _ptr(out), _ptr(work), G, Dm, float(temperature), float(eps), T, _stream()),
+              'clv_dsl_loss_fwd')
+        ctx.save_for_backward(work)
+        ctx.cfg = (G, Dm, float(temperature), T, video.dtype, text.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        work, = ctx.saved_tensors
+        G, Dm, temp, T, vdt, tdt = ctx.cfg
+        dout = _c(dloss.float().reshape(1))
+        L = _lib.lib()
+        bwd = L.clv_dsl_loss_bwd_large if ctx.large else L.clv_dsl_loss_bwd
+        dv = torch.empty(G, Dm, device=work.device, dtype=torch.float32)
+        dt = torch.empty_like(dv)
+        check(bwd(_ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), G, Dm, temp, T, _stream()), 'clv_dsl_loss_bwd')
+        return dv.to(vdt), dt.to(tdt), None, None, None
+
+
+def dual_softmax_temperature(T, sim_mat=False):
+    """The checked ``dual_softmax`` of a loss: a finite float >= 0 (the rule and the message of
+    ``evaluation.dual_softmax_scores``); refused together with a given score matrix."""
+    T = float(T)
+    if not 0 <= T < float('inf'):                             # false for NaN too
+        raise ValueError(f'dual_softmax: T must be finite and >= 0 (got {T})')
+    if sim_mat:
+        raise ValueError('NormSoftmaxLoss: sim_mat together with dual_softmax is refused: that matrix is already divided by '
+                         'a temperature, so the scale of the prior softmax(T * cosine) is undefined; pass the embeddings')
+    return T
+
+
+def norm_softmax_loss(video=None, text=None, sim_mat=None, temperature=0.07, eps=1e-12, dual_softmax=None):
+    """NormSoftmaxLoss (contrastive_loss.py:26-68) on already-gathered [G,Dm] embeddings or a [G,G] sim_mat.
+    ``dual_softmax = T`` (not in the reference): the same loss on the logits (G / temperature) c softmax(T c) with the prior
+    down the video axis (video -> text) and along the text axis (text -> video), c the cosine — the loss whose inference
+    form ``retrieval_rank(..., dual_softmax=T)`` is; T = 0 is the plain loss.  Embeddings only."""
+    if dual_softmax is None:
+        return _NormSoftmax.apply(video, text, sim_mat, temperature, eps)
+    T = dual_softmax_temperature(dual_softmax, sim_mat is not None)
+    return _DualSoftmaxLoss.apply(video, text, temperature, eps, T)
 
 
 # --------------------------------------------------------------------------- optimizer primitives

@@ -590,6 +590,33 @@ typedef struct ClvLossPlan {
 int clv_infonce_plan(int32_t G, int32_t Dm, int32_t ld, int32_t pair, int32_t large, ClvLossPlan* out);
 int clv_normsoftmax_plan(int32_t G, int32_t Dm, int32_t sim_mat, int32_t large, ClvLossPlan* out);
 
+/* Dual-softmax loss (DSL): NormSoftmaxLoss under the prior that clv_retrieval_* applies at evaluation (dual_softmax = T >= 0,
+ * finite; T multiplies the cosine).  Not in the reference.  Six symbols added to ABI 20 — new symbols, nothing existing
+ * changes, the version stays.  With c[i][j] the cosine of video i and text j (normalised with the clamp eps as above),
+ * a = G / temperature:
+ *   Pr[i][j] = softmax over i of T c[i][j]     Pc[i][j] = softmax over j of T c[i][j]
+ *   yr = a c Pr  (video -> text logits)        yc = a c Pc  (text -> video logits)
+ *   out[0] = -mean_i log_softmax_j(yr)[i][i] - mean_j log_softmax_i(yc)[j][j]
+ * T = 0 is NormSoftmaxLoss (P = 1 / G).  The gradient flows through the priors: with gr = (softmax_j(yr) - I) / G,
+ * gc = (softmax_i(yc) - I) / G, u[j] = sum_i gr c Pr, w[i] = sum_j gc c Pc,
+ *   d out / d c = a ( Pr (gr (1 + T c) - T u[j]) + Pc (gc (1 + T c) - T w[i]) ).
+ * video / text float [G][Dm]; out float [1]; dout float [1]; work >= clv_dsl_loss_work_floats(G, Dm) floats; the backward
+ * reads only the work the forward filled.  *_large: the multi-workgroup form (one wave per row, 64 adjacent columns per
+ * workgroup, a finish kernel that sums in a fixed order; LDS-tiled GEMMs), taken by the callers from
+ * clv_infonce_large_min_g() rows on; neither form uses float atomics, and a work either forward filled serves either
+ * backward.  clv_dsl_loss_plan: the launches of one evaluation, the record of clv_normsoftmax_plan without sim_mat (host
+ * only); the two statistics passes of the forward and the reductions of the backward run on the same launch shapes. */
+int64_t clv_dsl_loss_work_floats(int32_t G, int32_t Dm);
+int clv_dsl_loss_fwd(const float* video, const float* text, float* out, float* work, int32_t G, int32_t Dm,
+                     float temperature, float eps, float dual_softmax, void* stream);
+int clv_dsl_loss_bwd(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G, int32_t Dm,
+                     float temperature, float dual_softmax, void* stream);
+int clv_dsl_loss_fwd_large(const float* video, const float* text, float* out, float* work, int32_t G, int32_t Dm,
+                           float temperature, float eps, float dual_softmax, void* stream);
+int clv_dsl_loss_bwd_large(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G, int32_t Dm,
+                           float temperature, float dual_softmax, void* stream);
+int clv_dsl_loss_plan(int32_t G, int32_t Dm, int32_t large, ClvLossPlan* out);
+
 /* ------------------------------------------------------------------ optimizer
  * Grad-norm (clip_grad_norm_, mmcv_Fp16OptimizerHook.py:127-137) + AdamW step on flat
  * buffers (optimizer cfg pretrain_webvid_cc3m.py:129-137).
