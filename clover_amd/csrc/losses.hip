@@ -165,29 +165,27 @@ __global__ void __launch_bounds__(FC_WIDE) focal_bwd_pairs_kernel(
     }
 }
 
-// =========================================================================== InfoNCE
-// work layout (floats):
-//   en   [4][G][Dm]   normalised embeddings
-//   enT  [Dm][4][G]   their transpose (contraction index (k, j) contiguous)
-//   invn [4][G]       1/max(|e|, eps)
-//   sim  [3][G][G]    en0 . en_{k+1}^T / temperature
-//   lser [3][G]       row log-sum-exp of the three exclusive [G,3G] rows
-//   lsec [3][G]       column log-sum-exp (t2v)
-//   dsim [G][3][G]    d loss / d sim, row-major in (i, k, j)
-//   dsimT[3][G][G]    transposed per block: [k][j][i]
-//   den  [4][G][Dm]   d loss / d normalised embeddings
-//   acc  [16]
-//   term [6][G]       multi-workgroup path only: diag - lse of every exclusive row, then of every column
-struct NceWork {
-    float *en, *enT, *invn, *sim, *lser, *lsec, *dsim, *dsimT, *den, *acc, *term;
+// =========================================================================== the work area of a contrastive loss
+// One layout for every loss below, with nb score blocks against the first embedding (InfoNCE: 3, NormSoftmax and the
+// dual-softmax loss: 1).  In floats, in this order:
+//   en   [nb+1][G][Dm]  normalised embeddings
+//   enT  [Dm][nb+1][G]  their transpose (contraction index (k, j) contiguous)
+//   den  [nb+1][G][Dm]  d loss / d normalised embeddings
+//   invn [nb+1][G]      1/max(|e|, eps); NormSoftmax and the dual-softmax loss set its sign bit on the clamped rows
+//   sim  [nb][G][G]     en0 . en_{k+1}^T / temperature (the dual-softmax loss: the cosine)
+//   dsim [G][nb][G]     d loss / d sim, row-major in (i, k, j)
+//   dsimT[nb][G][G]     transposed per block: [k][j][i]
+//   lser [nb][G]        row log-sum-exp (InfoNCE: of the three exclusive [G,3G] rows)
+//   lsec [nb][G]        column log-sum-exp (t2v)
+//   16 spare
+//   term [2 nb][G]      multi-workgroup path only: diag - lse of every (exclusive) row, then of every column
+// loss_work_off is the one statement of it: the carve, the float count and the plan entries (which need the operand
+// addresses modulo 16 only) all read it.
+struct LossWork {
+    float *en, *enT, *den, *invn, *sim, *dsim, *dsimT, *lser, *lsec, *term;
 };
-__host__ __device__ inline int64_t nce_work_floats(int G, int Dm) {
-    return (int64_t)4 * G * Dm * 3 + (int64_t)4 * G + (int64_t)3 * G * G * 3 + (int64_t)6 * G + 16 + (int64_t)6 * G;
-}
-// Offsets (floats) of the parts of a work area with nb score blocks (InfoNCE: 3, NormSoftmax: 1), in the order of the
-// layout comments: the carves below and the plan entries (which need the operand addresses modulo 16 only) both read them.
 struct LossWorkOff {
-    int64_t en, enT, den, invn, sim, dsim, dsimT, lser, lsec, acc, term;
+    int64_t en, enT, den, invn, sim, dsim, dsimT, lser, lsec, term;
 };
 __host__ __device__ inline LossWorkOff loss_work_off(int nb, int G, int Dm) {
     const int64_t emb = (int64_t)(nb + 1) * G * Dm, blk = (int64_t)nb * G * G;
@@ -202,64 +200,63 @@ __host__ __device__ inline LossWorkOff loss_work_off(int nb, int G, int Dm) {
     o.dsimT = w; w += blk;
     o.lser = w; w += nb * G;
     o.lsec = w; w += nb * G;
-    o.acc = w; w += 16;
+    w += 16;
     o.term = w;
     return o;
 }
-__host__ __device__ inline NceWork nce_carve(float* w, int G, int Dm) {
-    const LossWorkOff o = loss_work_off(3, G, Dm);
-    NceWork W;
-    W.en = w + o.en;
-    W.enT = w + o.enT;
-    W.den = w + o.den;
-    W.invn = w + o.invn;
-    W.sim = w + o.sim;
-    W.dsim = w + o.dsim;
-    W.dsimT = w + o.dsimT;
-    W.lser = w + o.lser;
-    W.lsec = w + o.lsec;
-    W.acc = w + o.acc;
-    W.term = w + o.term;
-    return W;
+__host__ __device__ inline int64_t loss_work_floats(int nb, int G, int Dm) {
+    return loss_work_off(nb, G, Dm).term + (int64_t)2 * nb * G;
+}
+__host__ __device__ inline LossWork loss_carve(float* w, int nb, int G, int Dm) {
+    const LossWorkOff o = loss_work_off(nb, G, Dm);
+    return {w + o.en,   w + o.enT,   w + o.den,  w + o.invn, w + o.sim,
+            w + o.dsim, w + o.dsimT, w + o.lser, w + o.lsec, w + o.term};
 }
 
-// one wave per row: en = e / max(|e|, 1e-8)   (cos_norm, contrastive_loss.py:20-25)
-__device__ __forceinline__ void nce_normalize_body(const float* e0, const float* e1, const float* e2, const float* e3,
-                                                   const NceWork& W, int G, int Dm, int ld) {
+// one wave per row: en = e / max(|e|, eps) of NE embeddings with row stride ld.  InfoNCE: eps 1e-8 (cos_norm,
+// contrastive_loss.py:20-25); NormSoftmax: F.normalize's 1e-12 (:51-52) or sim_matrix's 1e-8 (:10-18).  MARK: the sign bit of
+// invn marks the clamped rows (nrm < eps) for the backward; without it the backward tests invn >= 1e8.  The two tests differ
+// at |e| == eps exactly, and each loss keeps its own.
+template <int NE, bool MARK>
+__device__ __forceinline__ void normalize_body(const float* e0, const float* e1, const float* e2, const float* e3,
+                                               const LossWork& W, int G, int Dm, int ld, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= 4 * G) return;
+    if (row >= NE * G) return;
     const int k = row / G, i = row - k * G;
-    const float* e = (k == 0 ? e0 : k == 1 ? e1 : k == 2 ? e2 : e3) + (int64_t)i * ld;
+    const float* e = (k == 0 ? e0 : (NE == 2 || k == 1) ? e1 : k == 2 ? e2 : e3) + (int64_t)i * ld;
     float s = 0.f;
     for (int d = lane; d < Dm; d += 64) s += e[d] * e[d];
     const float nrm = sqrtf(wave_sum(s));
-    const float inv = 1.0f / fmaxf(nrm, 1e-8f);
-    if (lane == 0) W.invn[row] = inv;
+    const float inv = 1.0f / fmaxf(nrm, eps);
+    if (lane == 0) W.invn[row] = (!MARK || nrm >= eps) ? inv : -inv;
     for (int d = lane; d < Dm; d += 64) {
         const float v = e[d] * inv;
         W.en[(int64_t)row * Dm + d] = v;
-        W.enT[((int64_t)d * 4 + k) * G + i] = v;
+        W.enT[((int64_t)d * NE + k) * G + i] = v;
     }
 }
-__global__ void __launch_bounds__(256) nce_normalize_kernel(const float* e0, const float* e1, const float* e2,
-                                                            const float* e3, NceWork W, int G, int Dm, int ld) {
-    nce_normalize_body(e0, e1, e2, e3, W, G, Dm, ld);
-}
 
+// =========================================================================== InfoNCE
 // The recognizer evaluates the loss TWICE per step on slots of one packed [G, k, Dm] tensor (video -> text and text -> video,
 // multimodal_transformer_pretrain.py:151,161): the *_pair kernels run both evaluations ("directions") in the same launches —
 // blockIdx.y (or the batch index of the GEMMs) is the direction, each with its own work area — so that the loss section
-// is 3 + 4 dependent launches instead of 6 + 8 (+ the zero fills and the add of the two gradients).
+// is 3 + 4 dependent launches instead of 6 + 8 (+ the zero fills and the add of the two gradients).  The forward of the
+// four-tensor entries is the same host sequence with one direction (direction 0 of an NcePair) on thin kernels of its own
+// over the shared bodies: through the *_pair kernels that form measured slower than before (profiles/loss_refactor.txt).
 struct NcePair {
-    NceWork w[2];
+    LossWork w[2];
     const float* e[2][4];
     const float* dout[4];      // backward: device scalars, the upstream gradients of {nce_0, rank_0, nce_1, rank_1} (null: 0)
-    int slot[2][4];
+    int slot[2][4];            // the packed form's norm backward only
 };
+__global__ void __launch_bounds__(256) nce_normalize_kernel(const float* e0, const float* e1, const float* e2,
+                                                            const float* e3, LossWork W, int G, int Dm, int ld) {
+    normalize_body<4, false>(e0, e1, e2, e3, W, G, Dm, ld, 1e-8f);
+}
 __global__ void __launch_bounds__(256) nce_pair_normalize_kernel(NcePair P, int G, int Dm, int ld) {
     const int d = blockIdx.y;
-    nce_normalize_body(P.e[d][0], P.e[d][1], P.e[d][2], P.e[d][3], P.w[d], G, Dm, ld);
+    normalize_body<4, false>(P.e[d][0], P.e[d][1], P.e[d][2], P.e[d][3], P.w[d], G, Dm, ld, 1e-8f);
 }
 
 // C[i][j] (ldc) = alpha * sum_k A[i][k] * B[j][k]   — exact-f32 MFMA 16x16x4, one 16x16 tile per workgroup.
@@ -330,7 +327,7 @@ __device__ __forceinline__ float nce_entry(const float* sim, int G, int kx, int 
 }
 
 // single block: all log-sum-exps, the two losses.
-__device__ __forceinline__ void nce_loss_body(const NceWork& W, float* __restrict__ out, int G, float margin) {
+__device__ __forceinline__ void nce_loss_body(const LossWork& W, float* __restrict__ out, int G, float margin) {
     __shared__ float sh[16];
     const float* sim = W.sim;
     float part_v = 0.f, part_t = 0.f, part_r = 0.f;
@@ -372,7 +369,7 @@ __device__ __forceinline__ void nce_loss_body(const NceWork& W, float* __restric
         out[1] = sr / (float)G;
     }
 }
-__global__ void __launch_bounds__(1024) nce_loss_kernel(NceWork W, float* __restrict__ out, int G, float margin) {
+__global__ void __launch_bounds__(1024) nce_loss_kernel(LossWork W, float* __restrict__ out, int G, float margin) {
     nce_loss_body(W, out, G, margin);
 }
 __global__ void __launch_bounds__(1024) nce_pair_loss_kernel(NcePair P, float* __restrict__ out, int G, float margin) {
@@ -380,7 +377,7 @@ __global__ void __launch_bounds__(1024) nce_pair_loss_kernel(NcePair P, float* _
 }
 
 // elementwise: d loss / d sim[k][i][j]
-__device__ __forceinline__ void nce_dsim_body(const NceWork& W, const float gn, const float gr, int G, float margin) {
+__device__ __forceinline__ void nce_dsim_body(const LossWork& W, const float gn, const float gr, int G, float margin) {
     const int64_t total = (int64_t)3 * G * G;
     const float invG = 1.0f / (float)G, inv3G = 1.0f / (float)(3 * G);
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -406,7 +403,7 @@ __device__ __forceinline__ void nce_dsim_body(const NceWork& W, const float gn, 
         W.dsimT[((int64_t)k * G + j) * G + i] = g;
     }
 }
-__global__ void __launch_bounds__(256) nce_dsim_kernel(NceWork W, const float* __restrict__ dout, int G, float margin) {
+__global__ void __launch_bounds__(256) nce_dsim_kernel(LossWork W, const float* __restrict__ dout, int G, float margin) {
     nce_dsim_body(W, dout[0], dout[1], G, margin);
 }
 __global__ void __launch_bounds__(256) nce_pair_dsim_kernel(NcePair P, int G, float margin) {
@@ -415,25 +412,27 @@ __global__ void __launch_bounds__(256) nce_pair_dsim_kernel(NcePair P, int G, fl
     nce_dsim_body(P.w[blockIdx.y], gn ? *gn : 0.f, gr ? *gr : 0.f, G, margin);
 }
 
-// d e = invn * (d en - en * <en, d en>)   (valid while |e| >= eps; below eps: d e = d en * invn)
-__global__ void __launch_bounds__(256) nce_norm_bwd_kernel(NceWork W, float* d0, float* d1, float* d2, float* d3,
-                                                           int G, int Dm, int ldd) {
+// d e = invn * (d en - en * <en, d en>)   (valid while |e| >= eps; below eps: d e = d en * invn) into NE separate gradients
+// with row stride ldd; NE and MARK as normalize_body.
+template <int NE, bool MARK>
+__global__ void __launch_bounds__(256) norm_bwd_kernel(LossWork W, float* d0, float* d1, float* d2, float* d3, int G,
+                                                       int Dm, int ldd) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= 4 * G) return;
+    if (row >= NE * G) return;
     const int k = row / G, i = row - k * G;
-    float* d = (k == 0 ? d0 : k == 1 ? d1 : k == 2 ? d2 : d3) + (int64_t)i * ldd;
+    float* d = (k == 0 ? d0 : (NE == 2 || k == 1) ? d1 : k == 2 ? d2 : d3) + (int64_t)i * ldd;
     const float* en = W.en + (int64_t)row * Dm;
     const float* de = W.den + (int64_t)row * Dm;
     float s = 0.f;
     for (int c = lane; c < Dm; c += 64) s += en[c] * de[c];
     s = wave_sum(s);
     const float inv = W.invn[row];
-    const bool clamped = inv >= 1e8f;
-    for (int c = lane; c < Dm; c += 64) d[c] = clamped ? de[c] * inv : inv * (de[c] - en[c] * s);
+    const bool clamped = MARK ? inv < 0.f : inv >= 1e8f;
+    for (int c = lane; c < Dm; c += 64) d[c] = clamped ? de[c] * (MARK ? -inv : inv) : inv * (de[c] - en[c] * s);
 }
 
-// The pair form writes the WHOLE packed gradient [G][k][Dm]: one wave per (row i, slot s) sums d en over the (direction,
+// The packed pair form writes the WHOLE packed gradient [G][k][Dm]: one wave per (row i, slot s) sums d en over the (direction,
 // position) pairs that read slot s (video and text are read by both directions; the map d e = invn (d en - en <en, d en>) is
 // linear in d en and en / invn of a slot are the same numbers in both work areas), a slot nobody read gets zeros.
 __global__ void __launch_bounds__(256) nce_pair_norm_bwd_kernel(NcePair P, float* __restrict__ dp, int G, int k, int Dm) {
@@ -476,53 +475,14 @@ __global__ void __launch_bounds__(256) nce_pair_norm_bwd_kernel(NcePair P, float
 // =========================================================================== NormSoftmaxLoss
 // (mmaction/models/losses/contrastive_loss.py:26-68): x = normalise(video) . normalise(text)^T / t,
 // loss = -mean_i diag(log_softmax(x, 1)) - mean_j diag(log_softmax(x^T, 1)).
-// work layout (floats):
-//   en [2][G][Dm], enT [Dm][2][G], den [2][G][Dm], invn [2][G], sim [G][G], dsim [G][G], dsimT [G][G],
-//   lser [G], lsec [G], 16 spare, term [2][G] (multi-workgroup path only: diag - lse of every row, then of every column)
-struct NsWork {
-    float *en, *enT, *den, *invn, *sim, *dsim, *dsimT, *lser, *lsec, *term;
-};
-__host__ __device__ inline int64_t ns_work_floats(int G, int Dm) {
-    return (int64_t)2 * G * Dm * 3 + (int64_t)2 * G + (int64_t)G * G * 3 + (int64_t)2 * G + 16 + (int64_t)2 * G;
-}
-__host__ __device__ inline NsWork ns_carve(float* w, int G, int Dm) {
-    const LossWorkOff o = loss_work_off(1, G, Dm);
-    NsWork W;
-    W.en = w + o.en;
-    W.enT = w + o.enT;
-    W.den = w + o.den;
-    W.invn = w + o.invn;
-    W.sim = w + o.sim;
-    W.dsim = w + o.dsim;
-    W.dsimT = w + o.dsimT;
-    W.lser = w + o.lser;
-    W.lsec = w + o.lsec;
-    W.term = w + o.term;
-    return W;
-}
-
-// one wave per row: en = e / max(|e|, eps)  (F.normalize eps 1e-12 :51-52, sim_matrix eps 1e-8 :10-18)
-__global__ void __launch_bounds__(256) ns_normalize_kernel(const float* e0, const float* e1, NsWork W, int G, int Dm,
+// The work area is the common one with nb = 1.
+__global__ void __launch_bounds__(256) ns_normalize_kernel(const float* e0, const float* e1, LossWork W, int G, int Dm,
                                                            float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= 2 * G) return;
-    const int k = row / G, i = row - k * G;
-    const float* e = (k == 0 ? e0 : e1) + (int64_t)i * Dm;
-    float s = 0.f;
-    for (int d = lane; d < Dm; d += 64) s += e[d] * e[d];
-    const float nrm = sqrtf(wave_sum(s));
-    const float inv = 1.0f / fmaxf(nrm, eps);
-    if (lane == 0) W.invn[row] = nrm >= eps ? inv : -inv;          // sign bit marks the clamped rows
-    for (int d = lane; d < Dm; d += 64) {
-        const float v = e[d] * inv;
-        W.en[(int64_t)row * Dm + d] = v;
-        W.enT[((int64_t)d * 2 + k) * G + i] = v;
-    }
+    normalize_body<2, true>(e0, e1, nullptr, nullptr, W, G, Dm, Dm, eps);
 }
 
 // single block: G row + G column log-sum-exps (one thread each), then the loss.
-__global__ void __launch_bounds__(1024) ns_loss_kernel(NsWork W, const float* __restrict__ sim, float* __restrict__ out,
+__global__ void __launch_bounds__(1024) ns_loss_kernel(LossWork W, const float* __restrict__ sim, float* __restrict__ out,
                                                        int G) {
     __shared__ float sh[16];
     float part = 0.f;
@@ -542,7 +502,7 @@ __global__ void __launch_bounds__(1024) ns_loss_kernel(NsWork W, const float* __
     if (threadIdx.x == 0) out[0] = -(tot / (float)G);
 }
 
-__global__ void __launch_bounds__(256) ns_dsim_kernel(NsWork W, const float* __restrict__ sim,
+__global__ void __launch_bounds__(256) ns_dsim_kernel(LossWork W, const float* __restrict__ sim,
                                                       const float* __restrict__ dout, float* __restrict__ dsim_out,
                                                       int G) {
     const int64_t total = (int64_t)G * G;
@@ -554,22 +514,6 @@ __global__ void __launch_bounds__(256) ns_dsim_kernel(NsWork W, const float* __r
         dsim_out[idx] = d;
         if (dsim_out == W.dsim) W.dsimT[(int64_t)j * G + i] = d;
     }
-}
-
-__global__ void __launch_bounds__(256) ns_norm_bwd_kernel(NsWork W, float* d0, float* d1, int G, int Dm) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= 2 * G) return;
-    const int k = row / G, i = row - k * G;
-    float* d = (k == 0 ? d0 : d1) + (int64_t)i * Dm;
-    const float* en = W.en + (int64_t)row * Dm;
-    const float* de = W.den + (int64_t)row * Dm;
-    float s = 0.f;
-    for (int c = lane; c < Dm; c += 64) s += en[c] * de[c];
-    s = wave_sum(s);
-    const float inv = W.invn[row];
-    const bool clamped = inv < 0.f;
-    for (int c = lane; c < Dm; c += 64) d[c] = clamped ? de[c] * -inv : inv * (de[c] - en[c] * s);
 }
 
 // =========================================================================== the loss section at a global batch
@@ -642,7 +586,7 @@ __device__ __forceinline__ void lse_cols_body(const float* __restrict__ sim, flo
     term[k * G + j] = blk[(int64_t)j * G + j] - lse;
 }
 
-__device__ __forceinline__ void nce_finish_body(const NceWork& W, float* __restrict__ out, int G, float margin) {
+__device__ __forceinline__ void nce_finish_body(const LossWork& W, float* __restrict__ out, int G, float margin) {
     __shared__ float sh[16];
     float part_v = 0.f, part_t = 0.f, part_r = 0.f;
     for (int t = threadIdx.x; t < 3 * G; t += blockDim.x) {
@@ -662,33 +606,33 @@ __device__ __forceinline__ void nce_finish_body(const NceWork& W, float* __restr
     }
 }
 
-__global__ void __launch_bounds__(256) nce_lse_rows_kernel(NceWork W, int G) {
+__global__ void __launch_bounds__(256) nce_lse_rows_kernel(LossWork W, int G) {
     lse_rows_body<3>(W.sim, W.lser, W.term, G);
 }
 __global__ void __launch_bounds__(256) nce_pair_lse_rows_kernel(NcePair P, int G) {
-    const NceWork& W = P.w[blockIdx.y];
+    const LossWork& W = P.w[blockIdx.y];
     lse_rows_body<3>(W.sim, W.lser, W.term, G);
 }
-__global__ void __launch_bounds__(64 * LSE_COL_WAVES) nce_lse_cols_kernel(NceWork W, int G) {
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) nce_lse_cols_kernel(LossWork W, int G) {
     lse_cols_body(W.sim, W.lsec, W.term + 3 * G, G);
 }
 __global__ void __launch_bounds__(64 * LSE_COL_WAVES) nce_pair_lse_cols_kernel(NcePair P, int G) {
-    const NceWork& W = P.w[blockIdx.z];
+    const LossWork& W = P.w[blockIdx.z];
     lse_cols_body(W.sim, W.lsec, W.term + 3 * G, G);
 }
-__global__ void __launch_bounds__(256) nce_finish_kernel(NceWork W, float* __restrict__ out, int G, float margin) {
+__global__ void __launch_bounds__(256) nce_finish_kernel(LossWork W, float* __restrict__ out, int G, float margin) {
     nce_finish_body(W, out, G, margin);
 }
 __global__ void __launch_bounds__(256) nce_pair_finish_kernel(NcePair P, float* __restrict__ out, int G, float margin) {
     nce_finish_body(P.w[blockIdx.x], out + 2 * blockIdx.x, G, margin);
 }
-__global__ void __launch_bounds__(256) ns_lse_rows_kernel(NsWork W, const float* __restrict__ sim, int G) {
+__global__ void __launch_bounds__(256) ns_lse_rows_kernel(LossWork W, const float* __restrict__ sim, int G) {
     lse_rows_body<1>(sim, W.lser, W.term, G);
 }
-__global__ void __launch_bounds__(64 * LSE_COL_WAVES) ns_lse_cols_kernel(NsWork W, const float* __restrict__ sim, int G) {
+__global__ void __launch_bounds__(64 * LSE_COL_WAVES) ns_lse_cols_kernel(LossWork W, const float* __restrict__ sim, int G) {
     lse_cols_body(sim, W.lsec, W.term + G, G);
 }
-__global__ void __launch_bounds__(256) ns_finish_kernel(NsWork W, float* __restrict__ out, int G) {
+__global__ void __launch_bounds__(256) ns_finish_kernel(LossWork W, float* __restrict__ out, int G) {
     __shared__ float sh[16];
     float part = 0.f;
     for (int t = threadIdx.x; t < 2 * G; t += blockDim.x) part += W.term[t];
@@ -783,7 +727,7 @@ __global__ void __launch_bounds__(256) sgemm_nt_tiled_kernel(const float* __rest
 // Backward, with gr = softmax_j(yr) - [i == j], gc = softmax_i(yc) - [i == j] (the 1 / G is folded into the scale):
 //   u[j] = sum_i (gr c) Pr      w[i] = sum_j (gc c) Pc
 //   d loss / d c = dout / temperature * ( Pr (gr (1 + x) - T u[j]) + Pc (gc (1 + x) - T w[i]) )
-// work layout: that of NormSoftmax (NsWork; lser / lsec hold the log-sums of yr / yc), then the prior statistics
+// work layout: that of NormSoftmax (LossWork with nb = 1; lser / lsec hold the log-sums of yr / yc), then the prior statistics
 // pc.m, pc.l, pr.m, pr.l, the maxima yr.m, yc.m, and w, u: [G] each.  The backward reads only what the forward
 // left there, and both forms leave the same numbers in the same places: either backward accepts either forward's work.
 // The arithmetic of this section is written with contraction off, one rounding per operation, so that tests/dsl_loss_ref.py
@@ -795,15 +739,15 @@ struct DslStat {
     float *m, *l;
 };
 struct DslWork {
-    NsWork ns;
+    LossWork ns;
     DslStat pc, pr, yr, yc;          // of x per row i / per column j; of yr per row i / of yc per column j
     float *w, *u;
 };
-__host__ __device__ inline int64_t dsl_work_floats(int G, int Dm) { return ns_work_floats(G, Dm) + (int64_t)8 * G; }
+__host__ __device__ inline int64_t dsl_work_floats(int G, int Dm) { return loss_work_floats(1, G, Dm) + (int64_t)8 * G; }
 __host__ __device__ inline DslWork dsl_carve(float* w, int G, int Dm) {
     DslWork W;
-    W.ns = ns_carve(w, G, Dm);
-    float* x = w + ns_work_floats(G, Dm);
+    W.ns = loss_carve(w, 1, G, Dm);
+    float* x = w + loss_work_floats(1, G, Dm);
     const int64_t g = G;
     W.pc = {x, x + g};
     W.pr = {x + 2 * g, x + 3 * g};
@@ -1094,7 +1038,7 @@ extern "C" int clv_focal_ce_bwd_ld(const void* logits, int32_t is_bf16, const in
     return focal_bwd_impl(logits, is_bf16, labels, row_ce, row_lse, count, dloss, dlogits, rows, V, ld, gamma, stream);
 }
 
-extern "C" int64_t clv_infonce_work_floats(int32_t G, int32_t Dm) { return nce_work_floats(G, Dm); }
+extern "C" int64_t clv_infonce_work_floats(int32_t G, int32_t Dm) { return loss_work_floats(3, G, Dm); }
 
 // one thread per exclusive row / column (6 G of them): whole waves, at most the kernel's 1024 (a per-rank batch of 8 needs one)
 static int nce_loss_threads(int G) {
@@ -1167,7 +1111,7 @@ static int nce_gemm(const float* A, const float* B, float* C, int M, int N, int 
     return clv_check_launch();
 }
 
-// The three GEMMs of an evaluation on a carved work area (NceWork: nb = 3 score blocks; NsWork: nb = 1).  which: 0 the
+// The three GEMMs of an evaluation on a carved work area with nb score blocks.  which: 0 the
 // scores en0 . en_{k+1}^T, 1 d en0 = dsim . en_{1..nb} (contraction nb * G), 2 d en_{k+1} = dsimT[k] . en0 (contraction G).
 // The launches and the plan entries both come through here.
 struct LossGemmArgs {
@@ -1185,13 +1129,36 @@ static LossGemmArgs loss_gemm_args(int which, int nb, int G, int Dm) {
     // d en_{k+1}[j][d] = sum_i dsimT[k][j][i] * en0[i][d] / T   :  A = dsimT[k] [G][G], B = enT[d][(0, i)]
     return {o.dsimT, o.enT, o.den + GD, G, Dm, G, G, (nb + 1) * G, Dm, nb, many ? GG : 0, 0, many ? GD : 0};
 }
-template <class WK>
-static int loss_gemm(const WK& W, int which, int nb, int G, int Dm, float alpha, hipStream_t st, int outer, int64_t s2,
-                     bool tiled) {
+static int loss_gemm(const LossWork& W, int which, int nb, int G, int Dm, float alpha, hipStream_t st, int outer,
+                     int64_t s2, bool tiled) {
     const LossGemmArgs a = loss_gemm_args(which, nb, G, Dm);
     float* work = W.en;                        // the work area starts with en
     return nce_gemm(work + a.oA, work + a.oB, work + a.oC, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.batch, a.sA, a.sB, a.sC,
                     alpha, st, outer, s2, tiled);
+}
+
+// The grid of an elementwise d loss / d sim kernel over nb G x G scores (256 threads, grid-stride above 1024 workgroups).
+static int loss_dsim_grid(int nb, int G) {
+    const int64_t grid = ((int64_t)nb * G * G + 255) / 256;
+    return grid > 1024 ? 1024 : (int)grid;
+}
+
+// The two gradient GEMMs after d loss / d sim: d en0 (GEMM 1), d en_{k+1} (GEMM 2).  outer / s2: as nce_gemm.
+static int loss_bwd_gemms(const LossWork& W, int nb, int G, int Dm, float alpha, hipStream_t st, int outer, int64_t s2,
+                          bool large) {
+    const int rc = loss_gemm(W, 1, nb, G, Dm, alpha, st, outer, s2, large);
+    return rc ? rc : loss_gemm(W, 2, nb, G, Dm, alpha, st, outer, s2, large);
+}
+
+// The backward tail of one evaluation: the two GEMMs, then the strided norm backward into NE gradients of row stride ldd
+// (InfoNCE: <4, false>; NormSoftmax and the dual-softmax loss: <2, true>, d2 and d3 unused).
+template <int NE, bool MARK>
+static int loss_bwd_tail(const LossWork& W, int G, int Dm, float alpha, hipStream_t st, bool large, float* d0, float* d1,
+                         float* d2, float* d3, int ldd) {
+    const int rc = loss_bwd_gemms(W, NE - 1, G, Dm, alpha, st, 1, 0, large);
+    if (rc) return rc;
+    hipLaunchKernelGGL((norm_bwd_kernel<NE, MARK>), dim3((NE * G + 3) / 4), dim3(256), 0, st, W, d0, d1, d2, d3, G, Dm, ldd);
+    return clv_check_launch();
 }
 
 // Launch shapes of the loss kernels between the GEMMs; the forwards below launch by this record.
@@ -1226,10 +1193,13 @@ static void loss_section_plan(int nb, int G, int Dm, int64_t s2, bool large, boo
     }
 }
 
+// The GEMM batch stride between the work areas of InfoNCE's nd directions (1: the four-tensor entries, 2: the pair entries).
+static int64_t nce_dir_stride(int nd, int G, int Dm) { return nd > 1 ? loss_work_floats(3, G, Dm) : 0; }
+
 // ld is checked as the entry checks it; no launch class depends on it
 extern "C" int clv_infonce_plan(int32_t G, int32_t Dm, int32_t ld, int32_t pair, int32_t large, ClvLossPlan* out) {
     if (!out || G <= 0 || Dm <= 0 || ld < Dm) return CLV_ERR_ARG;
-    loss_section_plan(3, G, Dm, pair ? nce_work_floats(G, Dm) : 0, large != 0, true, *out);
+    loss_section_plan(3, G, Dm, nce_dir_stride(pair ? 2 : 1, G, Dm), large != 0, true, *out);
     return 0;
 }
 
@@ -1239,83 +1209,94 @@ extern "C" int clv_normsoftmax_plan(int32_t G, int32_t Dm, int32_t sim_mat, int3
     return 0;
 }
 
-static int infonce_fwd_impl(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
-                            float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
-                            void* stream, bool large) {
-    if (!e0 || !e1 || !e2 || !e3 || !out || !work || G <= 0 || Dm <= 0 || ld < Dm || temperature <= 0.f)
-        return CLV_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    NceWork W = nce_carve(work, G, Dm);
-    hipLaunchKernelGGL(nce_normalize_kernel, dim3((4 * G + 3) / 4), dim3(256), 0, st, e0, e1, e2, e3, W, (int)G, (int)Dm,
-                       (int)ld);
+extern "C" int32_t clv_infonce_large_min_g(void) { return NCE_LARGE_MIN_G; }
+
+// The launches of InfoNCE on nd directions: 1 for the four-tensor entries (direction 0 of P alone), 2 for the packed pair
+// entries.
+static int infonce_fwd_impl(const NcePair& P, int nd, float* out, int G, int Dm, int ld, float temperature, float margin,
+                            hipStream_t st, bool large) {
+    const LossWork& W = P.w[0];
+    const bool one = nd == 1;
+    if (one)
+        hipLaunchKernelGGL(nce_normalize_kernel, dim3((4 * G + 3) / 4), dim3(256), 0, st, P.e[0][0], P.e[0][1], P.e[0][2],
+                           P.e[0][3], W, G, Dm, ld);
+    else
+        hipLaunchKernelGGL(nce_pair_normalize_kernel, dim3((4 * G + 3) / 4, nd), dim3(256), 0, st, P, G, Dm, ld);
     int rc = clv_check_launch();
     if (rc) return rc;
     // sim[k] = en0 . en_{k+1}^T / temperature
-    rc = loss_gemm(W, 0, 3, G, Dm, 1.0f / temperature, st, 1, 0, large);
+    rc = loss_gemm(W, 0, 3, G, Dm, 1.0f / temperature, st, nd, nce_dir_stride(nd, G, Dm), large);
     if (rc) return rc;
     ClvLossPlan pl;
     loss_kernels_plan(G, 3, large, pl);
     if (!large) {
-        hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(pl.loss_threads), 0, st, W, out, (int)G, margin);
+        if (one) hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(pl.loss_threads), 0, st, W, out, G, margin);
+        else hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(nd), dim3(pl.loss_threads), 0, st, P, out, G, margin);
         return clv_check_launch();
     }
-    hipLaunchKernelGGL(nce_lse_rows_kernel, dim3(pl.rows_grid), dim3(256), 0, st, W, (int)G);
+    if (one) hipLaunchKernelGGL(nce_lse_rows_kernel, dim3(pl.rows_grid), dim3(256), 0, st, W, G);
+    else hipLaunchKernelGGL(nce_pair_lse_rows_kernel, dim3(pl.rows_grid, nd), dim3(256), 0, st, P, G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G);
+    const dim3 colt(64 * LSE_COL_WAVES);
+    if (one) hipLaunchKernelGGL(nce_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), colt, 0, st, W, G);
+    else hipLaunchKernelGGL(nce_pair_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy, nd), colt, 0, st, P, G);
     if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_finish_kernel, dim3(1), dim3(pl.finish_threads), 0, st, W, out, (int)G, margin);
+    if (one) hipLaunchKernelGGL(nce_finish_kernel, dim3(1), dim3(pl.finish_threads), 0, st, W, out, G, margin);
+    else hipLaunchKernelGGL(nce_pair_finish_kernel, dim3(nd), dim3(pl.finish_threads), 0, st, P, out, G, margin);
     return clv_check_launch();
 }
 
-extern "C" int32_t clv_infonce_large_min_g(void) { return NCE_LARGE_MIN_G; }
+static int infonce_single_fwd(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
+                              float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
+                              void* stream, bool large) {
+    if (!e0 || !e1 || !e2 || !e3 || !out || !work || G <= 0 || Dm <= 0 || ld < Dm || temperature <= 0.f)
+        return CLV_ERR_ARG;
+    NcePair P{};                               // direction 0 alone
+    P.w[0] = loss_carve(work, 3, G, Dm);
+    P.e[0][0] = e0;
+    P.e[0][1] = e1;
+    P.e[0][2] = e2;
+    P.e[0][3] = e3;
+    return infonce_fwd_impl(P, 1, out, G, Dm, ld, temperature, margin, (hipStream_t)stream, large);
+}
 
 extern "C" int clv_infonce_fwd(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
                                float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
                                void* stream) {
-    return infonce_fwd_impl(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, false);
+    return infonce_single_fwd(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, false);
 }
 extern "C" int clv_infonce_fwd_large(const float* e0, const float* e1, const float* e2, const float* e3, float* out,
                                      float* work, int32_t G, int32_t Dm, int32_t ld, float temperature, float margin,
                                      void* stream) {
-    return infonce_fwd_impl(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, true);
+    return infonce_single_fwd(e0, e1, e2, e3, out, work, G, Dm, ld, temperature, margin, stream, true);
 }
 
-static int infonce_bwd_impl(const float* dout, const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G,
-                            int32_t Dm, int32_t ldd, float temperature, float margin, void* stream, bool large) {
+static int infonce_single_bwd(const float* dout, const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G,
+                              int32_t Dm, int32_t ldd, float temperature, float margin, void* stream, bool large) {
     if (!dout || !work || !d0 || !d1 || !d2 || !d3 || G <= 0 || Dm <= 0 || ldd < Dm) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    NceWork W = nce_carve(const_cast<float*>(work), G, Dm);
-    int64_t total = (int64_t)3 * G * G;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(nce_dsim_kernel, dim3(grid), dim3(256), 0, st, W, dout, (int)G, margin);
-    int rc = clv_check_launch();
+    const LossWork W = loss_carve(const_cast<float*>(work), 3, G, Dm);
+    hipLaunchKernelGGL(nce_dsim_kernel, dim3(loss_dsim_grid(3, G)), dim3(256), 0, st, W, dout, (int)G, margin);
+    const int rc = clv_check_launch();
     if (rc) return rc;
-    const float it = 1.0f / temperature;
-    rc = loss_gemm(W, 1, 3, G, Dm, it, st, 1, 0, large);
-    if (rc) return rc;
-    rc = loss_gemm(W, 2, 3, G, Dm, it, st, 1, 0, large);
-    if (rc) return rc;
-    hipLaunchKernelGGL(nce_norm_bwd_kernel, dim3((4 * G + 3) / 4), dim3(256), 0, st, W, d0, d1, d2, d3, (int)G, (int)Dm,
-                       (int)ldd);
-    return clv_check_launch();
+    return loss_bwd_tail<4, false>(W, G, Dm, 1.0f / temperature, st, large, d0, d1, d2, d3, ldd);
 }
 
 extern "C" int clv_infonce_bwd(const float* e0, const float* e1, const float* e2, const float* e3, const float* dout,
                                const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G, int32_t Dm,
                                int32_t ldd, float temperature, float margin, void* stream) {
-    return infonce_bwd_impl(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, false);
+    return infonce_single_bwd(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, false);
 }
 extern "C" int clv_infonce_bwd_large(const float* e0, const float* e1, const float* e2, const float* e3, const float* dout,
                                      const float* work, float* d0, float* d1, float* d2, float* d3, int32_t G, int32_t Dm,
                                      int32_t ldd, float temperature, float margin, void* stream) {
-    return infonce_bwd_impl(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, true);
+    return infonce_single_bwd(dout, work, d0, d1, d2, d3, G, Dm, ldd, temperature, margin, stream, true);
 }
 
 static bool nce_pair_setup(NcePair& P, const float* packed, float* work, const int32_t* slots, int G, int k, int Dm) {
-    const int64_t ws = nce_work_floats(G, Dm);
+    const int64_t ws = loss_work_floats(3, G, Dm);
     for (int d = 0; d < 2; ++d) {
-        P.w[d] = nce_carve(work + d * ws, G, Dm);
+        P.w[d] = loss_carve(work + d * ws, 3, G, Dm);
         for (int q = 0; q < 4; ++q) {
             const int sl = slots[d * 4 + q];
             if (sl < 0 || sl >= k) return false;
@@ -1329,63 +1310,34 @@ static bool nce_pair_setup(NcePair& P, const float* packed, float* work, const i
     return true;
 }
 
-static int infonce_pair_fwd_impl(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
-                                 int32_t k, int32_t Dm, float temperature, float margin, void* stream, bool large) {
+static int infonce_pair_fwd(const float* packed, const int32_t* slots, float* out, float* work, int32_t G, int32_t k,
+                            int32_t Dm, float temperature, float margin, void* stream, bool large) {
     if (!packed || !slots || !out || !work || G <= 0 || k < 4 || Dm <= 0 || temperature <= 0.f) return CLV_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     NcePair P;
     if (!nce_pair_setup(P, packed, work, slots, G, k, Dm)) return CLV_ERR_ARG;
-    const int64_t ws = nce_work_floats(G, Dm);
-    hipLaunchKernelGGL(nce_pair_normalize_kernel, dim3((4 * G + 3) / 4, 2), dim3(256), 0, st, P, (int)G, (int)Dm,
-                       (int)(k * Dm));
-    int rc = clv_check_launch();
-    if (rc) return rc;
-    rc = loss_gemm(P.w[0], 0, 3, G, Dm, 1.0f / temperature, st, 2, ws, large);
-    if (rc) return rc;
-    ClvLossPlan pl;
-    loss_kernels_plan(G, 3, large, pl);
-    if (!large) {
-        hipLaunchKernelGGL(nce_pair_loss_kernel, dim3(2), dim3(pl.loss_threads), 0, st, P, out, (int)G, margin);
-        return clv_check_launch();
-    }
-    hipLaunchKernelGGL(nce_pair_lse_rows_kernel, dim3(pl.rows_grid, 2), dim3(256), 0, st, P, (int)G);
-    if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_pair_lse_cols_kernel, dim3(pl.cols_gx, pl.cols_gy, 2), dim3(64 * LSE_COL_WAVES), 0, st, P,
-                       (int)G);
-    if ((rc = clv_check_launch())) return rc;
-    hipLaunchKernelGGL(nce_pair_finish_kernel, dim3(2), dim3(pl.finish_threads), 0, st, P, out, (int)G, margin);
-    return clv_check_launch();
+    return infonce_fwd_impl(P, 2, out, G, Dm, k * Dm, temperature, margin, (hipStream_t)stream, large);
 }
 
 extern "C" int clv_infonce_pair_fwd(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
                                     int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
-    return infonce_pair_fwd_impl(packed, slots, out, work, G, k, Dm, temperature, margin, stream, false);
+    return infonce_pair_fwd(packed, slots, out, work, G, k, Dm, temperature, margin, stream, false);
 }
 extern "C" int clv_infonce_pair_fwd_large(const float* packed, const int32_t* slots, float* out, float* work, int32_t G,
                                           int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
-    return infonce_pair_fwd_impl(packed, slots, out, work, G, k, Dm, temperature, margin, stream, true);
+    return infonce_pair_fwd(packed, slots, out, work, G, k, Dm, temperature, margin, stream, true);
 }
 
-static int infonce_pair_bwd_impl(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
-                                 int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream,
-                                 bool large) {
+static int infonce_pair_bwd(const float* const* dout, const float* work, const int32_t* slots, float* dpacked, int32_t G,
+                            int32_t k, int32_t Dm, float temperature, float margin, void* stream, bool large) {
     if (!dout || !work || !slots || !dpacked || G <= 0 || k < 4 || Dm <= 0 || temperature <= 0.f) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     NcePair P;
     if (!nce_pair_setup(P, nullptr, const_cast<float*>(work), slots, G, k, Dm)) return CLV_ERR_ARG;
     for (int q = 0; q < 4; ++q) P.dout[q] = dout[q];
-    const int64_t ws = nce_work_floats(G, Dm);
-    int64_t total = (int64_t)3 * G * G;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(nce_pair_dsim_kernel, dim3(grid, 2), dim3(256), 0, st, P, (int)G, margin);
+    hipLaunchKernelGGL(nce_pair_dsim_kernel, dim3(loss_dsim_grid(3, G), 2), dim3(256), 0, st, P, (int)G, margin);
     int rc = clv_check_launch();
     if (rc) return rc;
-    const float it = 1.0f / temperature;
-    const NceWork& W = P.w[0];
-    rc = loss_gemm(W, 1, 3, G, Dm, it, st, 2, ws, large);
-    if (rc) return rc;
-    rc = loss_gemm(W, 2, 3, G, Dm, it, st, 2, ws, large);
+    rc = loss_bwd_gemms(P.w[0], 3, G, Dm, 1.0f / temperature, st, 2, nce_dir_stride(2, G, Dm), large);
     if (rc) return rc;
     hipLaunchKernelGGL(nce_pair_norm_bwd_kernel, dim3((k * G + 3) / 4), dim3(256), 0, st, P, dpacked, (int)G, (int)k,
                        (int)Dm);
@@ -1394,15 +1346,15 @@ static int infonce_pair_bwd_impl(const float* const* dout, const float* work, co
 
 extern "C" int clv_infonce_pair_bwd(const float* const* dout, const float* work, const int32_t* slots, float* dpacked,
                                     int32_t G, int32_t k, int32_t Dm, float temperature, float margin, void* stream) {
-    return infonce_pair_bwd_impl(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, false);
+    return infonce_pair_bwd(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, false);
 }
 extern "C" int clv_infonce_pair_bwd_large(const float* const* dout, const float* work, const int32_t* slots,
                                           float* dpacked, int32_t G, int32_t k, int32_t Dm, float temperature, float margin,
                                           void* stream) {
-    return infonce_pair_bwd_impl(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, true);
+    return infonce_pair_bwd(dout, work, slots, dpacked, G, k, Dm, temperature, margin, stream, true);
 }
 
-extern "C" int64_t clv_normsoftmax_work_floats(int32_t G, int32_t Dm) { return ns_work_floats(G, Dm > 0 ? Dm : 1); }
+extern "C" int64_t clv_normsoftmax_work_floats(int32_t G, int32_t Dm) { return loss_work_floats(1, G, Dm > 0 ? Dm : 1); }
 
 static int normsoftmax_fwd_impl(const float* video, const float* text, const float* sim_mat, float* out,
                                 float* work, int32_t G, int32_t Dm, float temperature, float eps, void* stream,
@@ -1410,7 +1362,7 @@ static int normsoftmax_fwd_impl(const float* video, const float* text, const flo
     if (!out || !work || G <= 0) return CLV_ERR_ARG;
     if (!sim_mat && (!video || !text || Dm <= 0 || temperature <= 0.f || eps <= 0.f)) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    NsWork W = ns_carve(work, G, Dm > 0 ? Dm : 1);
+    LossWork W = loss_carve(work, 1, G, Dm > 0 ? Dm : 1);
     if (!sim_mat) {
         hipLaunchKernelGGL(ns_normalize_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, video, text, W, (int)G, (int)Dm,
                            eps);
@@ -1450,22 +1402,13 @@ static int normsoftmax_bwd_impl(const float* sim_mat, const float* dout, const f
     if (!dout || !work || G <= 0) return CLV_ERR_ARG;
     if (sim_mat ? !dsim : (!dvideo || !dtext || Dm <= 0 || temperature <= 0.f)) return CLV_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    NsWork W = ns_carve(const_cast<float*>(work), G, Dm > 0 ? Dm : 1);
-    const int64_t total = (int64_t)G * G;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(ns_dsim_kernel, dim3(grid), dim3(256), 0, st, W, sim_mat ? sim_mat : (const float*)W.sim, dout,
-                       sim_mat ? dsim : W.dsim, (int)G);
-    int rc = clv_check_launch();
+    LossWork W = loss_carve(const_cast<float*>(work), 1, G, Dm > 0 ? Dm : 1);
+    hipLaunchKernelGGL(ns_dsim_kernel, dim3(loss_dsim_grid(1, G)), dim3(256), 0, st, W,
+                       sim_mat ? sim_mat : (const float*)W.sim, dout, sim_mat ? dsim : W.dsim, (int)G);
+    const int rc = clv_check_launch();
     if (rc || sim_mat) return rc;
-    const float it = 1.0f / temperature;
     // d en_v[i][d] = sum_j dsim[i][j] en_t[j][d] / t ;  d en_t[j][d] = sum_i dsim[i][j] en_v[i][d] / t
-    rc = loss_gemm(W, 1, 1, G, Dm, it, st, 1, 0, large);
-    if (rc) return rc;
-    rc = loss_gemm(W, 2, 1, G, Dm, it, st, 1, 0, large);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ns_norm_bwd_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, W, dvideo, dtext, (int)G, (int)Dm);
-    return clv_check_launch();
+    return loss_bwd_tail<2, true>(W, G, Dm, 1.0f / temperature, st, large, dvideo, dtext, nullptr, nullptr, Dm);
 }
 
 extern "C" int clv_normsoftmax_bwd(const float* sim_mat, const float* dout, const float* work, float* dvideo,
@@ -1550,18 +1493,11 @@ static int dsl_bwd_impl(const float* dout, const float* work, float* dvideo, flo
         hipLaunchKernelGGL(dsl_u_cols_kernel, dim3(pl.cols_gx, pl.cols_gy), dim3(64 * LSE_COL_WAVES), 0, st, W, (int)G, T, a);
         if ((rc = clv_check_launch())) return rc;
     }
-    const int64_t total = (int64_t)G * G;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(dsl_dsim_kernel, dim3(grid), dim3(256), 0, st, W, dout, (int)G, T, a, 1.0f / temperature);
+    hipLaunchKernelGGL(dsl_dsim_kernel, dim3(loss_dsim_grid(1, G)), dim3(256), 0, st, W, dout, (int)G, T, a,
+                       1.0f / temperature);
     if ((rc = clv_check_launch())) return rc;
     // d en_v[i][d] = sum_j dc[i][j] en_t[j][d] ;  d en_t[j][d] = sum_i dc[i][j] en_v[i][d]
-    rc = loss_gemm(W.ns, 1, 1, G, Dm, 1.0f, st, 1, 0, large);
-    if (rc) return rc;
-    rc = loss_gemm(W.ns, 2, 1, G, Dm, 1.0f, st, 1, 0, large);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ns_norm_bwd_kernel, dim3((2 * G + 3) / 4), dim3(256), 0, st, W.ns, dvideo, dtext, (int)G, (int)Dm);
-    return clv_check_launch();
+    return loss_bwd_tail<2, true>(W.ns, G, Dm, 1.0f, st, large, dvideo, dtext, nullptr, nullptr, Dm);
 }
 
 extern "C" int clv_dsl_loss_bwd(const float* dout, const float* work, float* dvideo, float* dtext, int32_t G, int32_t Dm,

@@ -2328,8 +2328,10 @@ def nce_large_min_g():
 
 
 def _nce_fn(name, G):
+    """(forward entry, backward entry) of loss `name` at G rows: both of the same set."""
     large = NCE_FORCE_LARGE if NCE_FORCE_LARGE is not None else G >= nce_large_min_g()
-    return getattr(_lib.lib(), name + '_large' if large else name), bool(large)
+    L, tail = _lib.lib(), '_large' if large else ''
+    return getattr(L, name + '_fwd' + tail), getattr(L, name + '_bwd' + tail)
 
 
 class _InfoNCE(torch.autograd.Function):
@@ -2341,7 +2343,7 @@ class _InfoNCE(torch.autograd.Function):
         L = _lib.lib()
         work = torch.empty(L.clv_infonce_work_floats(G, Dm), device=e0.device, dtype=torch.float32)
         out = torch.empty(2, device=e0.device, dtype=torch.float32)
-        fwd, ctx.large = _nce_fn('clv_infonce_fwd', G)
+        fwd, ctx.bwd = _nce_fn('clv_infonce', G)
         check(fwd(_ptr(es[0]), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), _ptr(out), _ptr(work), G, Dm, Dm,
                   float(temperature), float(margin), _stream()), 'clv_infonce_fwd')
         ctx.save_for_backward(*es, work)
@@ -2354,10 +2356,8 @@ class _InfoNCE(torch.autograd.Function):
         G, Dm, temp, margin, dts = ctx.cfg
         dout = torch.stack([dnce.float().reshape(()), drank.float().reshape(())]).contiguous()
         ds = [torch.empty_like(e0) for _ in range(4)]
-        L = _lib.lib()
-        check((L.clv_infonce_bwd_large if ctx.large else L.clv_infonce_bwd)(
-            _ptr(e0), _ptr(e1), _ptr(e2), _ptr(e3), _ptr(dout), _ptr(work), _ptr(ds[0]), _ptr(ds[1]), _ptr(ds[2]),
-            _ptr(ds[3]), G, Dm, Dm, temp, margin, _stream()), 'clv_infonce_bwd')
+        check(ctx.bwd(_ptr(e0), _ptr(e1), _ptr(e2), _ptr(e3), _ptr(dout), _ptr(work), _ptr(ds[0]), _ptr(ds[1]), _ptr(ds[2]),
+                      _ptr(ds[3]), G, Dm, Dm, temp, margin, _stream()), 'clv_infonce_bwd')
         return ds[0].to(dts[0]), ds[1].to(dts[1]), ds[2].to(dts[2]), ds[3].to(dts[3]), None, None
 
 
@@ -2376,7 +2376,7 @@ class _InfoNCEPacked(torch.autograd.Function):
         out = torch.empty(2, device=packed.device, dtype=torch.float32)
         base = packed.data_ptr()
         es = [C.c_void_p(base + 4 * Dm * int(sl)) for sl in slots]
-        fwd, ctx.large = _nce_fn('clv_infonce_fwd', G)
+        fwd, ctx.bwd = _nce_fn('clv_infonce', G)
         check(fwd(*es, _ptr(out), _ptr(work), G, Dm, k * Dm, float(temperature), float(margin), _stream()),
               'clv_infonce_fwd')
         ctx.save_for_backward(work)
@@ -2391,9 +2391,8 @@ class _InfoNCEPacked(torch.autograd.Function):
         dp = torch.zeros(G, k, Dm, device=work.device, dtype=torch.float32)
         base = dp.data_ptr()
         ds = [C.c_void_p(base + 4 * Dm * sl) for sl in slots]
-        L = _lib.lib()
-        check((L.clv_infonce_bwd_large if ctx.large else L.clv_infonce_bwd)(
-            None, None, None, None, _ptr(dout), _ptr(work), *ds, G, Dm, k * Dm, temp, margin, _stream()), 'clv_infonce_bwd')
+        check(ctx.bwd(None, None, None, None, _ptr(dout), _ptr(work), *ds, G, Dm, k * Dm, temp, margin, _stream()),
+              'clv_infonce_bwd')
         return dp, None, None, None
 
 
@@ -2412,7 +2411,7 @@ class _InfoNCEPair(torch.autograd.Function):
         slots = (C.c_int32 * 8)(*[int(v) for v in tuple(slots_a) + tuple(slots_b)])
         work = torch.empty(2 * L.clv_infonce_work_floats(G, Dm), device=packed.device, dtype=torch.float32)
         out = torch.empty(4, device=packed.device, dtype=torch.float32)
-        fwd, ctx.large = _nce_fn('clv_infonce_pair_fwd', G)
+        fwd, ctx.bwd = _nce_fn('clv_infonce_pair', G)
         check(fwd(_ptr(packed), slots, _ptr(out), _ptr(work), G, k, Dm, float(temperature), float(margin), _stream()),
               'clv_infonce_pair_fwd')
         ctx.save_for_backward(work)
@@ -2427,9 +2426,7 @@ class _InfoNCEPair(torch.autograd.Function):
         ds = [d if d is None or d.dtype == torch.float32 else d.float() for d in douts]
         dout = (C.c_void_p * 4)(*[None if d is None else d.data_ptr() for d in ds])
         dp = torch.empty(G, k, Dm, device=work.device, dtype=torch.float32)
-        L = _lib.lib()
-        check((L.clv_infonce_pair_bwd_large if ctx.large else L.clv_infonce_pair_bwd)(
-            dout, _ptr(work), slots, _ptr(dp), G, k, Dm, temp, margin, _stream()), 'clv_infonce_pair_bwd')
+        check(ctx.bwd(dout, _ptr(work), slots, _ptr(dp), G, k, Dm, temp, margin, _stream()), 'clv_infonce_pair_bwd')
         return dp, None, None, None, None
 
 
@@ -2472,7 +2469,7 @@ class _NormSoftmax(torch.autograd.Function):
         dev = (x if x is not None else v).device
         work = torch.empty(L.clv_normsoftmax_work_floats(G, Dm), device=dev, dtype=torch.float32)
         out = torch.empty(1, device=dev, dtype=torch.float32)
-        fwd, ctx.large = _nce_fn('clv_normsoftmax_fwd', G)
+        fwd, ctx.bwd = _nce_fn('clv_normsoftmax', G)
         check(fwd(_ptr(v), _ptr(t), _ptr(x), _ptr(out), _ptr(work), G, Dm, float(temperature), float(eps), _stream()),
               'clv_normsoftmax_fwd')
         ctx.save_for_backward(work, *([x] if x is not None else []))
@@ -2485,16 +2482,14 @@ class _NormSoftmax(torch.autograd.Function):
         work, *rest = ctx.saved_tensors
         G, Dm, temp, dts, sdt = ctx.cfg
         dout = _c(dloss.float().reshape(1))
-        L = _lib.lib()
-        bwd = L.clv_normsoftmax_bwd_large if ctx.large else L.clv_normsoftmax_bwd
         if rest:
             dsim = torch.empty_like(rest[0])
-            check(bwd(_ptr(rest[0]), _ptr(dout), _ptr(work), None, None, _ptr(dsim), G, Dm, temp,
-                                        _stream()), 'clv_normsoftmax_bwd')
+            check(ctx.bwd(_ptr(rest[0]), _ptr(dout), _ptr(work), None, None, _ptr(dsim), G, Dm, temp, _stream()),
+                  'clv_normsoftmax_bwd')
             return None, None, dsim.to(sdt), None, None
         dv = torch.empty(G, Dm, device=work.device, dtype=torch.float32)
         dt = torch.empty_like(dv)
-        check(bwd(None, _ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), None, G, Dm, temp, _stream()),
+        check(ctx.bwd(None, _ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), None, G, Dm, temp, _stream()),
               'clv_normsoftmax_bwd')
         return dv.to(dts[0]), dt.to(dts[1]), None, None, None
 
@@ -2512,7 +2507,7 @@ class _DualSoftmaxLoss(torch.autograd.Function):
         G, Dm = v.shape
         work = torch.empty(L.clv_dsl_loss_work_floats(G, Dm), device=v.device, dtype=torch.float32)
         out = torch.empty(1, device=v.device, dtype=torch.float32)
-        fwd, ctx.large = _nce_fn('clv_dsl_loss_fwd', G)
+        fwd, ctx.bwd = _nce_fn('clv_dsl_loss', G)
         check(fwd(_ptr(v), _ptr(t), _ptr(out), _ptr(work), G, Dm, float(temperature), float(eps), T, _stream()),
               'clv_dsl_loss_fwd')
         ctx.save_for_backward(work)
@@ -2524,11 +2519,9 @@ class _DualSoftmaxLoss(torch.autograd.Function):
         work, = ctx.saved_tensors
         G, Dm, temp, T, vdt, tdt = ctx.cfg
         dout = _c(dloss.float().reshape(1))
-        L = _lib.lib()
-        bwd = L.clv_dsl_loss_bwd_large if ctx.large else L.clv_dsl_loss_bwd
         dv = torch.empty(G, Dm, device=work.device, dtype=torch.float32)
         dt = torch.empty_like(dv)
-        check(bwd(_ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), G, Dm, temp, T, _stream()), 'clv_dsl_loss_bwd')
+        check(ctx.bwd(_ptr(dout), _ptr(work), _ptr(dv), _ptr(dt), G, Dm, temp, T, _stream()), 'clv_dsl_loss_bwd')
         return dv.to(vdt), dt.to(tdt), None, None, None
 
 

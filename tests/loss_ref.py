@@ -178,10 +178,10 @@ FOCAL_ROWS = (1, 9)
 # order is an operation the kernels really perform, and at temperature 0.05 it is the largest term of their error: a
 # one-thread sum of 3 G exponentials, a per-lane running (max, sum), a contraction walked sixteen elements at a time.
 #   order = dict(large=<multi-workgroup path>, nw=(waves that split the contraction of the score GEMM, of d en0, of d en_k))
-# csrc/losses.hip: nce_normalize_body / ns_normalize_kernel (lane-strided sum of squares, wave_sum), sgemm_nt_kernel and
+# csrc/losses.hip: normalize_body (lane-strided sum of squares, wave_sum), sgemm_nt_kernel and
 # sgemm_nt_tiled_kernel (fused multiply-adds in the order of the MFMA steps, the partial tiles of the waves added in wave
 # order), nce_loss_body / ns_loss_kernel (`s += __expf(..)` over a row or a column by one thread), lse_push / lse_rows_body /
-# lse_cols_body (running maximum with a rescaled sum per lane or wave, then the merge), nce_norm_bwd_kernel (lane-strided
+# lse_cols_body (running maximum with a rescaled sum per lane or wave, then the merge), norm_bwd_kernel (lane-strided
 # dot product).
 NEG_INF = float('-inf')
 

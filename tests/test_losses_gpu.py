@@ -303,6 +303,60 @@ def test_infonce_clamp_rows(large):
     bud.done()
 
 
+WORK_FILL = 0x4B3C2D1E                          # a finite float (about 1.2e7): what no kernel wrote stays comparable
+
+
+def filled(floats):
+    return torch.full((floats,), WORK_FILL, dtype=torch.int32, device=DEV).view(torch.float32)
+
+
+def same_bits(a, b):
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+@pytest.mark.parametrize('G,Dm,large', [(17, 80, False), (17, 80, True), (65, 48, True)])
+def test_infonce_single_is_one_direction_of_pair(G, Dm, large):
+    """The four-tensor entry on the slots of a direction leaves, bit for bit, the losses and the WHOLE work area that the
+    pair entry leaves for that direction: after the forward, and again after the backward (d sim, its transpose, d en).
+    G = 65 on the multi-workgroup form: a second, one-lane trip of the row kernel and a second, one-column workgroup of
+    the column kernel."""
+    lib, sfx = L(), '_large' if large else ''
+    pl = lr.nce_plan(lib, G, Dm, 0, large)
+    assert pl.large == int(large)
+    if G == 65:
+        assert pl.cols_gx == 2 and pl.cols_last == 1 and pl.rows_grid == (3 * G + 3) // 4
+        assert (G + 63) // 64 == 2 and G % 64 == 1          # a row's 64 lanes stride its G scores: a second trip of one lane
+    p = lr.nce_packed(G, Dm).to(DEV)
+    k, wf = p.shape[1], lib.clv_infonce_work_floats(G, Dm)
+    temperature, wts = 0.05, lr.WEIGHTS['distinct']
+    slots = (C.c_int32 * 8)(*(lr.SA + lr.SB))
+    pwork, pout = filled(2 * wf), torch.full((4,), float('nan'), device=DEV)
+    assert getattr(lib, 'clv_infonce_pair_fwd' + sfx)(ptr(p), slots, ptr(pout), ptr(pwork), G, k, Dm, temperature,
+                                                        lr.NCE_MARGIN, stream()) == 0
+    single = []
+    for d, sl in enumerate((lr.SA, lr.SB)):
+        work, out = filled(wf), torch.full((2,), float('nan'), device=DEV)
+        es = [C.c_void_p(p.data_ptr() + 4 * Dm * s) for s in sl]
+        assert getattr(lib, 'clv_infonce_fwd' + sfx)(*es, ptr(out), ptr(work), G, Dm, k * Dm, temperature, lr.NCE_MARGIN,
+                                                      stream()) == 0
+        torch.cuda.synchronize()
+        assert same_bits(out, pout[2 * d:2 * d + 2]), (d, out.tolist(), pout.tolist())
+        assert same_bits(work, pwork[d * wf:(d + 1) * wf]), ('forward', d)
+        single.append(work)
+    ws = [torch.tensor([w], device=DEV) for w in wts]
+    dout = (C.c_void_p * 4)(*[w.data_ptr() for w in ws])
+    dp = torch.empty(G, k, Dm, device=DEV)
+    assert getattr(lib, 'clv_infonce_pair_bwd' + sfx)(dout, ptr(pwork), slots, ptr(dp), G, k, Dm, temperature,
+                                                        lr.NCE_MARGIN, stream()) == 0
+    for d, work in enumerate(single):
+        d2 = torch.tensor(wts[2 * d:2 * d + 2], device=DEV)
+        ds = [torch.empty(G, Dm, device=DEV) for _ in range(4)]
+        assert getattr(lib, 'clv_infonce_bwd' + sfx)(None, None, None, None, ptr(d2), ptr(work), *[ptr(g) for g in ds], G, Dm,
+                                                      Dm, temperature, lr.NCE_MARGIN, stream()) == 0
+        torch.cuda.synchronize()
+        assert same_bits(work, pwork[d * wf:(d + 1) * wf]), ('backward', d)
+
+
 @pytest.mark.parametrize('G,Dm,force', [(17, 300, False), (17, 300, True), (131, 80, None), (96, 768, None)])
 def test_infonce_through_ops(G, Dm, force):
     from clover_amd import ops
