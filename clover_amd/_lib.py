@@ -120,6 +120,11 @@ class ClvLossPlan(C.Structure):
         'idle_row_lanes', 'idle_col_waves')]
 
 
+class ClvOptimPlan(C.Structure):
+    """Mirror of ``struct ClvOptimPlan`` (include/clover_hip.h): the launch of one optimizer pass over n elements."""
+    _fields_ = [(n, _i32) for n in ('grid', 'block', 'trips', 'tail')]
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),
@@ -236,6 +241,7 @@ SIGNATURES = {
     'clv_pack_bf16': (C.c_int, [_p, _p, _i64, _p]),
     'clv_sumsq_bf16': (C.c_int, [_p, _p, _i64, _p]),
     'clv_adamw_step_dev_bf16g': (C.c_int, [_p] * 6 + [_i64] + [_f] * 5 + [_p]),
+    'clv_optim_plan': (C.c_int, [_i32, _i64, C.POINTER(ClvOptimPlan)]),
     'clv_sgemm_strided': (C.c_int, [_p] * 4 + [_i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
     'clv_sgemm_strided_rowsum': (C.c_int, [_p] * 4 + [_i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
     'clv_sgemm_nt': (C.c_int, [_p] * 4 + [_i64, _i32, _i32, _i64, _i64, _i64, _p]),

@@ -72,13 +72,19 @@ struct AdamArgs {
     float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, max_norm, grad_scale;
 };
 
+// One element of the update:
+//   g *= coef;  p *= 1 - lr wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  p -= (lr / bc1) (m / (sqrt(v) / bc2_sqrt + eps))
+// Which products are fused into their sum is written out, and the compiler's own contraction is off: left to it, the choice
+// differed between the float4 body and the tail of one kernel, and between the fp32- and the 16-bit-gradient instantiation
+// (there for two lanes of each float4), so the same values gave different bits (tests/OPTIM_ERROR_BUDGET.md, Defects).  The
+// fusions chosen are the ones the float4 body of the fp32 kernels already had.
 __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, const AdamArgs& a, float coef) {
+#pragma clang fp contract(off)
     g *= coef;
-    p *= (1.f - a.lr * a.wd);
-    m = a.beta1 * m + (1.f - a.beta1) * g;
-    v = a.beta2 * v + (1.f - a.beta2) * g * g;
+    m = fmaf(1.f - a.beta1, g, a.beta1 * m);
+    v = fmaf(g, (1.f - a.beta2) * g, a.beta2 * v);
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p -= (a.lr / a.bc1) * (m / denom);
+    p = fmaf(fmaf(-a.lr, a.wd, 1.f), p, -((a.lr / a.bc1) * (m / denom)));
     return p;
 }
 
@@ -230,7 +236,29 @@ int grid_for(int64_t n4, int64_t cap = (1 << 20)) {
     return (int)b;
 }
 
+// The launch of one pass over n elements: what clv_optim_plan reports, and where every launcher below takes its grid from.
+enum { OPT_SUMSQ = 0, OPT_ADAMW = 1, OPT_PACK = 2 };
+constexpr int64_t PACK_MAX_N4 = (int64_t)(1 << 20) * 256;     // pack_bf16_kernel has no grid-stride loop: one float4 per thread
+bool optim_launch(int kind, int64_t n, ClvOptimPlan* o) {
+    const int64_t n4 = n / 4;
+    if (kind == OPT_SUMSQ) o->grid = grid_for(n4, SUMSQ_GRID);
+    else if (kind == OPT_ADAMW) o->grid = grid_for(n4);
+    else if (kind == OPT_PACK && (n + 3) / 4 <= PACK_MAX_N4) o->grid = grid_for((n + 3) / 4);
+    else return false;
+    const int64_t threads = (int64_t)o->grid * 256;
+    o->block = 256;
+    o->trips = (int32_t)((n4 + threads - 1) / threads);
+    o->tail = (int32_t)(n % 4);
+    return true;
+}
+
 }  // namespace
+
+extern "C" int clv_optim_plan(int32_t kind, int64_t n, ClvOptimPlan* out) {
+    if (!out || n < 0) return CLV_ERR_ARG;
+    if (kind < OPT_SUMSQ || kind > OPT_PACK) return CLV_ERR_ARG;
+    return optim_launch(kind, n, out) ? CLV_OK : CLV_ERR_UNSUPPORTED;
+}
 
 extern "C" int clv_abi_version(void) { return CLV_ABI_VERSION; }
 extern "C" int clv_half_type(void) { return CLV_HALF_IS_F16; }
@@ -239,7 +267,9 @@ extern "C" int clv_sumsq(const float* g, float* acc, int64_t n, void* stream) {
     if (!g || !acc || n < 0) return CLV_ERR_ARG;
     if (n == 0) return CLV_OK;
     if (((uintptr_t)g) & 15) return CLV_ERR_ARG;
-    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(grid_for(n / 4, SUMSQ_GRID)), dim3(256), 0, (hipStream_t)stream, g, acc, n);
+    ClvOptimPlan pl;
+    optim_launch(OPT_SUMSQ, n, &pl);
+    hipLaunchKernelGGL(sumsq_kernel<float>, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream, g, acc, n);
     return clv_check_launch();
 }
 
@@ -247,7 +277,9 @@ extern "C" int clv_sumsq_bf16(const void* g, float* acc, int64_t n, void* stream
     if (!g || !acc || n < 0) return CLV_ERR_ARG;
     if (n == 0) return CLV_OK;
     if (((uintptr_t)g) & 7) return CLV_ERR_ARG;
-    hipLaunchKernelGGL(sumsq_kernel<bf16_t>, dim3(grid_for(n / 4, SUMSQ_GRID)), dim3(256), 0, (hipStream_t)stream,
+    ClvOptimPlan pl;
+    optim_launch(OPT_SUMSQ, n, &pl);
+    hipLaunchKernelGGL(sumsq_kernel<bf16_t>, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream,
                        (const bf16_t*)g, acc, n);
     return clv_check_launch();
 }
@@ -256,7 +288,9 @@ extern "C" int clv_pack_bf16(const float* src, void* dst, int64_t n, void* strea
     if (!src || !dst || n < 0) return CLV_ERR_ARG;
     if (n == 0) return CLV_OK;
     if ((((uintptr_t)src) & 15) || (((uintptr_t)dst) & 7)) return CLV_ERR_ARG;
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n);
+    ClvOptimPlan pl;
+    if (!optim_launch(OPT_PACK, n, &pl)) return CLV_ERR_UNSUPPORTED;      // beyond one float4 per thread of the largest grid
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream, src, (bf16_t*)dst, n);
     return clv_check_launch();
 }
 
@@ -268,7 +302,9 @@ extern "C" int clv_adamw_step(float* p, const float* g, float* m, float* v, void
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return CLV_ERR_ARG;
     if (shadow && (((uintptr_t)shadow) & 7)) return CLV_ERR_ARG;
     AdamArgs a{lr, beta1, beta2, eps, weight_decay, bias_c1, sqrtf(bias_c2), max_norm, grad_scale};
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+    ClvOptimPlan pl;
+    optim_launch(OPT_ADAMW, n, &pl);
+    hipLaunchKernelGGL(adamw_kernel, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream, p, g, m, v,
                        (bf16_t*)shadow, sumsq, n, a);
     return clv_check_launch();
 }
@@ -303,7 +339,9 @@ extern "C" int clv_adamw_step_dev(float* p, const float* g, float* m, float* v, 
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return CLV_ERR_ARG;
     if (shadow && (((uintptr_t)shadow) & 7)) return CLV_ERR_ARG;
     AdamArgs a{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, 0.f, 1.f};
-    hipLaunchKernelGGL(adamw_dev_kernel<float>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+    ClvOptimPlan pl;
+    optim_launch(OPT_ADAMW, n, &pl);
+    hipLaunchKernelGGL(adamw_dev_kernel<float>, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream, p, g, m, v,
                        (bf16_t*)shadow, (const OptimState*)state, n, a);
     return clv_check_launch();
 }
@@ -316,7 +354,9 @@ extern "C" int clv_adamw_step_dev_bf16g(float* p, const void* g, float* m, float
     if ((((uintptr_t)p) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return CLV_ERR_ARG;
     if ((((uintptr_t)g) & 7) || (shadow && (((uintptr_t)shadow) & 7))) return CLV_ERR_ARG;
     AdamArgs a{lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, 0.f, 1.f};
-    hipLaunchKernelGGL(adamw_dev_kernel<bf16_t>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, p,
+    ClvOptimPlan pl;
+    optim_launch(OPT_ADAMW, n, &pl);
+    hipLaunchKernelGGL(adamw_dev_kernel<bf16_t>, dim3(pl.grid), dim3(pl.block), 0, (hipStream_t)stream, p,
                        (const bf16_t*)g, m, v, (bf16_t*)shadow, (const OptimState*)state, n, a);
     return clv_check_launch();
 }

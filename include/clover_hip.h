@@ -875,6 +875,18 @@ int clv_pack_bf16(const float* src, void* dst, int64_t n, void* stream);
 int clv_sumsq_bf16(const void* g, float* acc, int64_t n, void* stream);
 int clv_adamw_step_dev_bf16g(float* p, const void* g, float* m, float* v, void* shadow, const void* state, int64_t n,
                              float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+/* clv_optim_plan (host only, no GPU needed; one symbol added to ABI 20 — a new symbol, nothing existing changes, the version
+ * stays): the launch of one optimizer pass over n elements.  kind 0: clv_sumsq /
+ * clv_sumsq_bf16; 1: clv_adamw_step / clv_adamw_step_dev / clv_adamw_step_dev_bf16g; 2: clv_pack_bf16.  The launchers take
+ * their grid from the helper this entry reports, so the two cannot drift apart.
+ *   grid, block  workgroups (kind 0: at most 2048, grid-stride; kind 1: at most 2^20, grid-stride; kind 2: one 4-element
+ *                group per thread and no loop — n beyond 2^30 is CLV_ERR_UNSUPPORTED, here and in clv_pack_bf16) and threads
+ *   trips        4-element groups the busiest thread walks (0 when n < 4)
+ *   tail         n % 4: elements the first `tail` threads of workgroup 0 take one by one */
+typedef struct ClvOptimPlan {
+    int32_t grid, block, trips, tail;
+} ClvOptimPlan;
+int clv_optim_plan(int32_t kind, int64_t n, ClvOptimPlan* out);
 
 /* ------------------------------------------------------------------ video QA / fill-in-the-blank fine-tuning (csrc/qa.hip)
  * clv_qa_answer_rows: the row table of the QA head into the fusion output [N, Ltot, D] viewed as [N * Ltot, D], built on

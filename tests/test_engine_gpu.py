@@ -122,6 +122,22 @@ def test_transposed_weight_shadows_follow_the_optimizer():
     check()
 
 
+def test_every_slab_shadow_is_the_rounded_slab_after_a_step():
+    """After a step the 16-bit shadow of EVERY segment is its fp32 slab rounded to nearest even, bit for bit over the
+    whole slab — not only at the parameters with a transposed copy."""
+    from clover_amd.engine import CloverEngine
+    b = batch(tag='sh')
+    eng = CloverEngine(make_model(), b, lr=1e-3, weight_decay=0.005, grad_clip=15.0, max_iters=100)
+    before = [sg.flat_p.clone() for sg in eng.segments]
+    eng.step(b)
+    torch.cuda.synchronize()
+    assert eng.segments
+    for sg, p0 in zip(eng.segments, before):
+        n = sg.flat_p.numel()
+        assert not torch.equal(sg.flat_p, p0)                                # the step was taken
+        assert torch.equal(sg.shadow[:n].view(torch.int16), sg.flat_p.to(HALF).view(torch.int16))
+
+
 def test_skipped_step_keeps_adam_count_and_dry_step_has_no_side_effects():
     """A non-finite gradient norm skips the update on the device and does not advance Adam's step count (the
     reference skips optimizer.step(), mmcv_Fp16OptimizerHook.py:123-141) while the LR index moves on; dry_step —
