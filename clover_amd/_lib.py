@@ -125,6 +125,17 @@ class ClvOptimPlan(C.Structure):
     _fields_ = [(n, _i32) for n in ('grid', 'block', 'trips', 'tail')]
 
 
+class ClvClipPrepGeom(C.Structure):
+    """Mirror of ``struct ClvClipPrepGeom`` (include/clover_hip.h): the shape of one clv_clip_prep call."""
+    _fields_ = [(n, _i32) for n in ('B', 'T', 'Hs', 'Ws', 'C', 'S', 'out_dtype', 'pad')] + [('boxes_host', _p)]
+
+
+class ClvClipPrepPlan(C.Structure):
+    """Mirror of ``struct ClvClipPrepPlan`` (include/clover_hip.h): what clv_clip_prep launches for a shape."""
+    _fields_ = [(n, _i32) for n in ('cls', 'grid', 'block', 'lanes_per_row', 'rows_per_pass', 'passes', 'strips',
+                                    'tail_rows', 'idle_lanes')]
+
+
 class ClvLnExtra(C.Structure):
     """Mirror of ``struct ClvLnExtra`` (include/clover_hip.h)."""
     _fields_ = [('xscale', _p), ('rows_per_sample', _i32), ('drop_p', _f), ('seed', _p), ('dy2', _p), ('dres', _p),
@@ -269,6 +280,9 @@ SIGNATURES = {
     'clv_retrieval_col_stats': (C.c_int, [_p, _p, _i64, _i64, _i32, _i64, _i64, _f, _p, _p, _p, _p]),
     'clv_retrieval_rank_prior_work_bytes': (C.c_int64, [_i64, _i64, _i32, _i32]),
     'clv_retrieval_rank_prior': (C.c_int, [_p] * 8 + [_i64, _i64, _i32, _i64, _i64, _i32, _p, _p, _f, _p]),
+    'clv_clip_prep_supported': (C.c_int, [_i32] * 6),
+    'clv_clip_prep_plan': (C.c_int, [C.POINTER(ClvClipPrepGeom), C.POINTER(ClvClipPrepPlan)]),
+    'clv_clip_prep': (C.c_int, [_p] * 6 + [C.POINTER(ClvClipPrepGeom), _p]),
 }
 
 _lib = None

@@ -966,10 +966,17 @@ class CloverEngine:
         if cap.stale_views:
             torch._foreach_zero_(cap.stale_views)
 
-    def input_buffers(self):
+    def input_buffers(self, shapes=None):
         """The static input tensors of the active hipGraphs (None before capture): a loader that writes its host-to-device
-        copies straight into them — and hands the same dict to step() — saves the per-step staging copy."""
-        return self._active.batch if self.graph is not None else None
+        copies straight into them — and hands the same dict to step() — saves the per-step staging copy.  With ``shapes``
+        ({key: shape} of a batch): those of the capture of THAT geometry, active or not, or None when it has none yet
+        (a loader of one of two alternating streams asks for its own, utils/packed_loader.py)."""
+        if self.graph is None:
+            return None
+        if shapes is None:
+            return self._active.batch
+        cap = self._captures.get(tuple((k, tuple(s)) for k, s in sorted(shapes.items())))
+        return cap.batch if cap is not None else None
 
     def _graphed_forward_backward(self, batch):
         """encode (hipGraph) -> gather + contrastive losses (eager: it holds the step's only forward

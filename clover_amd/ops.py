@@ -3144,3 +3144,92 @@ def retrieval_group_best(query, gallery, lo=None, hi=None, want_rank=False, eps=
                                      Nq, Ng, D, max(q.stride(0), D), max(g.stride(0), D), float(eps), _stream()),
           'clv_retrieval_group_best')
     return bidx, bscore, rank
+
+
+# --------------------------------------------------------------------------- clip preparation (csrc/clip_prep.hip)
+CLIP_REASONS = {1: 'CLV_CLIP_BAD_CHANNELS: the kernel reads 3-channel frames',
+                2: 'CLV_CLIP_BAD_FRAME: the frame needs at least one pixel each way',
+                3: 'CLV_CLIP_BAD_SIZE: the output size must be a multiple of 8 in [8, 2048]',
+                4: 'CLV_CLIP_BAD_BOX: a crop box needs 1 <= right - left <= Ws and 1 <= bottom - top <= Hs'}
+_CLIP_CONSTANTS = {}
+
+
+def clip_prep_refusal(C_, Hs, Ws, S, box_w=1, box_h=1):
+    """None when clv_clip_prep covers the shape (and a box of box_w x box_h), else the named reason.  The set is stated
+    once, in clv_clip_prep_supported (host only: no GPU needed)."""
+    rc = _lib.lib().clv_clip_prep_supported(int(C_), int(Hs), int(Ws), int(S), int(box_w), int(box_h))
+    return None if rc == 0 else CLIP_REASONS.get(rc, str(rc))
+
+
+def clip_prep_plan(B, T, Hs, Ws, S, half=False):
+    """The launch of clv_clip_prep for a shape (clv_clip_prep_plan, host only) as a dict of the plan's fields."""
+    g = _lib.ClvClipPrepGeom(B=B, T=T, Hs=Hs, Ws=Ws, C=3, S=S, out_dtype=int(half), pad=0, boxes_host=None)
+    pl = _lib.ClvClipPrepPlan()
+    check(_lib.lib().clv_clip_prep_plan(C.byref(g), C.byref(pl)), 'clv_clip_prep_plan')
+    return {n: getattr(pl, n) for n, _ in pl._fields_}
+
+
+def clip_prep_constants(mean, std, device):
+    """(mean, inv_std) as fp32 [3] tensors on `device`: inv_std = 1 / float64(std) rounded to fp32, mmcv.imnormalize's
+    `stdinv` (the reference multiplies by it: Normalize, augmentations.py:1563-1600).  Cached per (mean, std, device)."""
+    key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), _dev_key(device))
+    if key not in _CLIP_CONSTANTS:
+        if len(key[0]) != 3 or len(key[1]) != 3:
+            raise ValueError('clip_prep: mean and std have one value per channel (3)')
+        m = torch.tensor(key[0], dtype=torch.float64).to(torch.float32)
+        s = (1.0 / torch.tensor(key[1], dtype=torch.float64)).to(torch.float32)
+        _CLIP_CONSTANTS[key] = (m.to(device), s.to(device))
+    return _CLIP_CONSTANTS[key]
+
+
+def clip_prep(src_u8, boxes, flips, mean, std, out=None, size=224, dtype=None):
+    """Decoded frames -> the normalised clip [B, 1, 3, T, size, size] in one launch (clv_clip_prep): per sample a crop box,
+    a bilinear resize of the crop to size x size (half-pixel centres, neighbours clamped to the crop), an optional
+    horizontal flip, (v - mean[c]) / std[c] and the NCTHW layout — the reference's RandomResizedCrop / CenterCrop, Resize,
+    Flip, Normalize and FormatShape.
+
+    src_u8 uint8 [B, T, Hs, Ws, 3] on the device, channel order as stored; boxes int [B, 4] (left, top, right, bottom;
+    right / bottom exclusive) ON THE HOST (array or CPU tensor: checked here, then uploaded — a device tensor is copied
+    back first, which synchronises); flips [B] (host or device, non-zero = mirror); mean / std 3 numbers each.
+    With `out` given ([B, 1, 3, T, size, size], fp32 or the 16-bit element type, contiguous) the clip is written in
+    place — a captured engine's static `imgs` buffer goes here; otherwise a new tensor of `dtype` (default fp32).
+    No autograd: inputs carry no gradient.  A box outside the frame raises ValueError before any launch; a shape or box
+    extent outside the kernel's set raises NotImplementedError with the named reason of clv_clip_prep_supported."""
+    _need_gpu(src_u8, out)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 5:
+        raise TypeError(f'clip_prep: src is uint8 [B, T, Hs, Ws, 3] (got {src_u8.dtype} {tuple(src_u8.shape)})')
+    B, T, Hs, Ws, Cin = src_u8.shape
+    if out is not None:
+        size, dtype = out.shape[-1], out.dtype
+    dtype = torch.float32 if dtype is None else dtype
+    S = int(size)
+    why = clip_prep_refusal(Cin, Hs, Ws, S)
+    if why is not None:
+        raise NotImplementedError(f'clip_prep: {why}')
+    if dtype not in (torch.float32, BF16):
+        raise TypeError(f'clip_prep: the output is fp32 or {BF16} (got {dtype})')
+    hb = torch.as_tensor(boxes).detach().cpu().to(torch.int32).contiguous()
+    if hb.shape != (B, 4):
+        raise ValueError(f'clip_prep: boxes must be [{B}, 4] (got {tuple(hb.shape)})')
+    for b, (l, t, r, bt) in enumerate(hb.tolist()):
+        if l < 0 or t < 0 or r > Ws or bt > Hs:
+            raise ValueError(f'clip_prep: box {b} = {(l, t, r, bt)} leaves the {Hs} x {Ws} frame')
+        why = clip_prep_refusal(Cin, Hs, Ws, S, r - l, bt - t)
+        if why is not None:
+            raise NotImplementedError(f'clip_prep: box {b} = {(l, t, r, bt)}: {why}')
+    dev = src_u8.device
+    fl = torch.as_tensor(flips)
+    if fl.shape != (B,):
+        raise ValueError(f'clip_prep: flips must be [{B}] (got {tuple(fl.shape)})')
+    fl = _c((fl != 0).to(torch.uint8).to(dev, non_blocking=True))
+    db = hb.to(dev, non_blocking=True)
+    mean_d, inv_std_d = clip_prep_constants(mean, std, dev)
+    if out is None:
+        out = torch.empty(B, 1, 3, T, S, S, device=dev, dtype=dtype)
+    elif tuple(out.shape) != (B, 1, 3, T, S, S) or not out.is_contiguous():
+        raise ValueError(f'clip_prep: out must be contiguous [{B}, 1, 3, {T}, {S}, {S}] (got {tuple(out.shape)})')
+    g = _lib.ClvClipPrepGeom(B=B, T=T, Hs=Hs, Ws=Ws, C=Cin, S=S, out_dtype=int(dtype != torch.float32), pad=0,
+                             boxes_host=hb.data_ptr())
+    check(_lib.lib().clv_clip_prep(_ptr(_c(src_u8)), _ptr(db), _ptr(fl), _ptr(mean_d), _ptr(inv_std_d), _ptr(out),
+                                   C.byref(g), _stream()), 'clv_clip_prep')
+    return out

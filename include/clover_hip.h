@@ -1030,6 +1030,64 @@ int clv_retrieval_rank_prior(const float* query, const float* gallery, const int
                              int64_t ldq, int64_t ldg, int32_t topk, const float* col_max, const float* col_sum, float T,
                              void* stream);
 
+/* ------------------------------------------------------------------ clip preparation (csrc/clip_prep.hip)
+ * Decoded uint8 frames -> the normalised clip the recognizers take, in one launch: the reference's
+ * RandomResizedCrop / CenterCrop -> Resize(S, bilinear) -> Flip -> Normalize -> FormatShape('NCTHW_TSN')
+ * (mmaction/datasets/pipelines/augmentations.py:894-942, 1090-1180, 1560-1640, 1690-1740; formating.py FormatShape), run on
+ * the device from one crop box and one flip flag per sample.  Three symbols added to ABI 20 — new symbols, nothing existing
+ * changes, the version stays.
+ *   src      uint8 [B, T, Hs, Ws, 3]: channel-last as decoded, channel order as stored (the reference normalises with
+ *            to_rgb=False); mean / inv_std follow that order
+ *   boxes    int32 [B, 4] (left, top, right, bottom) in source pixels, right / bottom exclusive; one box per sample, shared
+ *            by its T frames
+ *   flips    uint8 [B], non-zero = mirror horizontally
+ *   mean, inv_std  float [3]
+ *   out      [B, 1, 3, T, S, S], fp32 (out_dtype 0) or the library's 16-bit element type (out_dtype 1); 16-byte aligned
+ * Per output element (c, t, y, x) of sample b, with bw = right - left, bh = bottom - top:
+ *   xe = flips[b] ? S - 1 - x : x;   sx = clamp((xe + 0.5) * bw / S - 0.5, 0, bw - 1)   (half-pixel centres, clamped to the
+ *   crop's first and last pixel centre);  x0 = floor(sx), x1 = min(x0 + 1, bw - 1), fx = sx - x0;  sy, y0, y1, fy likewise.
+ *   The four neighbours are clamped to the CROP BOX, not the frame — the geometry of mmcv.imresize(crop, 'bilinear').
+ *   v = bilinear blend in fp32;  out = (v - mean[c]) * inv_std[c], rounded once on store.  No antialiasing (the reference
+ *   has none).  The blend stays in fp32 where the reference rounds the resized image to uint8 first (deviation D2).
+ * Supported set — clv_clip_prep_supported is its single statement (host only, no GPU needed; box_w = right - left, box_h =
+ * bottom - top of one box); it returns 0 or
+ *   CLV_CLIP_BAD_CHANNELS  C != 3
+ *   CLV_CLIP_BAD_FRAME     Hs < 1 or Ws < 1
+ *   CLV_CLIP_BAD_SIZE      S not a multiple of 8 in [8, 2048] (a lane owns 8 adjacent x: every store a 16-byte vector)
+ *   CLV_CLIP_BAD_BOX       not 1 <= box_w <= Ws and 1 <= box_h <= Hs
+ * Any Hs, Ws, T, B (B * T * strips < 2^31).
+ * clv_clip_prep_plan (host only): the launch of a shape — the launcher takes its grid from the same helper.
+ *   cls            CLV_CLIP_CLASS_PLANE: S * S / 8 <= 256, one workgroup per frame writes the whole plane in one pass;
+ *                  CLV_CLIP_CLASS_STRIPS: `strips` workgroups per frame, each `passes` passes of `rows_per_pass` rows
+ *   grid, block    workgroups (B * T * strips) and threads
+ *   lanes_per_row  S / 8;  idle_lanes: threads of a workgroup behind its last whole row
+ *   tail_rows      rows of a frame's last strip when that strip is a partial one, else 0
+ * clv_clip_prep: the launcher (asynchronous on `stream`, allocates nothing, capturable).  Outside the supported set:
+ * CLV_ERR_UNSUPPORTED; NULL / misaligned pointers, B or T < 1, an unknown out_dtype: CLV_ERR_ARG.  `boxes` lives on the
+ * device, so the launcher cannot read it without a sync: a caller that has the boxes on the host hands them in
+ * geom->boxes_host (int32 [B, 4], may be NULL) and gets CLV_ERR_UNSUPPORTED for a box extent outside the set and
+ * CLV_ERR_ARG for a box outside the frame, before any launch.  Whatever `boxes` holds, the kernel clamps the box into the
+ * frame and to at least one pixel, so no box reads outside src. */
+#define CLV_CLIP_BAD_CHANNELS 1
+#define CLV_CLIP_BAD_FRAME 2
+#define CLV_CLIP_BAD_SIZE 3
+#define CLV_CLIP_BAD_BOX 4
+#define CLV_CLIP_OUT_F32 0
+#define CLV_CLIP_OUT_HALF 1
+#define CLV_CLIP_CLASS_PLANE 0
+#define CLV_CLIP_CLASS_STRIPS 1
+typedef struct ClvClipPrepGeom {
+    int32_t B, T, Hs, Ws, C, S, out_dtype, pad;
+    const int32_t* boxes_host;
+} ClvClipPrepGeom;
+typedef struct ClvClipPrepPlan {
+    int32_t cls, grid, block, lanes_per_row, rows_per_pass, passes, strips, tail_rows, idle_lanes;
+} ClvClipPrepPlan;
+int clv_clip_prep_supported(int32_t C, int32_t Hs, int32_t Ws, int32_t S, int32_t box_w, int32_t box_h);
+int clv_clip_prep_plan(const ClvClipPrepGeom* geom, ClvClipPrepPlan* out);
+int clv_clip_prep(const uint8_t* src, const int32_t* boxes, const uint8_t* flips, const float* mean, const float* inv_std,
+                  void* out, const ClvClipPrepGeom* geom, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

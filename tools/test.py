@@ -8,7 +8,9 @@
 The model runs ``forward_test(separate_test=True)`` (the HIP Swin + BERT paths, forward only) over a test set sharded
 rank-major; embeddings are collected over RCCL and rank 0 computes R@1/5/10, median rank.  The dataset side is out of
 scope: ``data.synthetic_test`` describes a synthetic test set (``pairs`` random (clip, caption) pairs, so the metrics
-of an untrained model sit at chance: R@K ~ 100 K / pairs).
+of an untrained model sit at chance: R@K ~ 100 K / pairs).  A config with ``data.packed = dict(path=..., test=dict(...))``
+(configs/finetune_retrieval_packed_synthetic.py) reads its test split from packed uint8 clips instead: centre crop, resize
+and normalisation run on the device (``ops.clip_prep``, clover_amd/utils/packed_loader.py).
 
 Zero-shot multiple choice (``evaluation = dict(metrics=['video_qa_mc'], test_fn='recall_for_video_text_retrieval')``, the
 reference's finetune_msrvtt_mc.py; ``synthetic_test.candidates = C`` captions per video) and the many-caption protocol
@@ -122,10 +124,15 @@ def main():
             print(f'loaded {args.checkpoint}: {len(res.missing_keys)} missing, {len(res.unexpected_keys)} unexpected keys')
     model.eval()
     st = cfg.data.get('synthetic_test', dict(pairs=64, frames=8, tokens=32))
-    loader = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
-                                 st.get('tokens', 32), rank, world, dev, qa=st.get('qa') if kind == 'qa' else None,
-                                 candidates=st.get('candidates') if mc else None,
-                                 captions=st.get('captions') if varied else None)
+    packed = cfg.data.get('packed')
+    if packed and packed.get('test'):                     # uint8 clips from disk: centre crop + resize on the device
+        from clover_amd.utils.packed_loader import packed_loaders
+        loader = packed_loaders(packed, 'test', cfg.get('videos_per_gpu', 8), dev, rank, world)[0]
+    else:
+        loader = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
+                                     st.get('tokens', 32), rank, world, dev, qa=st.get('qa') if kind == 'qa' else None,
+                                     candidates=st.get('candidates') if mc else None,
+                                     captions=st.get('captions') if varied else None)
     on_device = bool(args.topk) or mc or varied           # scored on the device: only small integer vectors come back
     if kind == 'qa':
         results = multi_gpu_test_itm_finetune(model, loader)

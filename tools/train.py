@@ -7,8 +7,12 @@
 
 Same config format (`_base_`, `model = dict(type='CloverPretrain', ...)`, `optimizer` with `base_lr`, `lr_config`,
 `total_epochs`, `workflow`, `checkpoint_config`, `log_config`), same CLI names.  The dataset side (decoding,
-tokenisation, augmentation pipelines) is outside this project's scope: `data.synthetic` describes loaders of
-synthetic batches with the real batch layout instead."""
+tokenisation) is outside this project's scope: `data.synthetic` describes loaders of synthetic batches with the real
+batch layout instead, and `data.packed = dict(path=..., train=dict(...), test=dict(...))` trains on pre-decoded uint8 clips
+whose crop / resize / flip / normalise steps run on the device (clover_amd/utils/packed_loader.py, `ops.clip_prep`):
+
+    python tools/pack_synthetic_clips.py work_dirs/packed_synthetic
+    python tools/train.py configs/finetune_retrieval_packed_synthetic.py --launcher none --validate"""
 import argparse
 import os
 import sys
@@ -131,9 +135,15 @@ def main():
     model = clover_amd.build_model(cfg.model.copy() if hasattr(cfg.model, 'copy') else dict(cfg.model)).to(dev)
     model.train()
     lr = scaled_lr(cfg, world)                           # tools/train.py:160-166
-    syn = cfg.data['synthetic']
-    loaders = [SyntheticLoader(s['length'], cfg.get('videos_per_gpu', 1), s.get('frames', 8), s.get('tokens', 32),
-                               1000 * (i + 1) + rank, dev, qa=s.get('qa')) for i, s in enumerate(syn)]
+    packed = cfg.data.get('packed')
+    if packed:                                           # uint8 clips from disk, prepared on the device (ops.clip_prep)
+        from clover_amd.utils.packed_loader import packed_loaders
+        loaders = packed_loaders(packed, 'train', cfg.get('videos_per_gpu', 1), dev, rank, world,
+                                 seed=args.seed or 0)
+    else:
+        syn = cfg.data['synthetic']
+        loaders = [SyntheticLoader(s['length'], cfg.get('videos_per_gpu', 1), s.get('frames', 8), s.get('tokens', 32),
+                                   1000 * (i + 1) + rank, dev, qa=s.get('qa')) for i, s in enumerate(syn)]
     lrc = cfg.lr_config
     kw = engine_kwargs(cfg, lr, clover_amd._lib.HALF_F16)
     engine = CloverEngine(model, next(iter(loaders[0])), **kw)      # (virtual ranks: built and captured on ONE micro-batch)
@@ -143,7 +153,10 @@ def main():
         first = next(iter(loaders[0]))
         engine.dry_step(first)                           # no optimizer step: training starts from the initial weights
         engine.capture(first)
-    if kw['virtual_ranks'] > 1:                          # lists of k batches per step: runner.iter counts optimizer steps
+        if packed and kw['virtual_ranks'] == 1:          # the clips go straight into the graphs' static `imgs` buffers
+            for ld in loaders:                           # (k micro-batches per step cannot share one buffer)
+                ld.engine = engine
+    if kw['virtual_ranks'] > 1:                         # lists of k batches per step: runner.iter counts optimizer steps
         loaders = [GroupedLoader(ld, kw['virtual_ranks'], printer=print if rank == 0 else None) for ld in loaders]
     runner = CloverRunner(engine, model=model, work_dir=cfg.work_dir, max_epochs=cfg.total_epochs,
                           meta=dict(config_name=os.path.basename(args.config), seed=args.seed))
@@ -164,10 +177,14 @@ def main():
         ev_metrics = [ev.get('metrics')] if isinstance(ev.get('metrics'), str) else list(ev.get('metrics') or [])
         mc = embed and 'video_qa_mc' in ev_metrics
         varied = embed and 'recall_for_video_text_retrieval_varied' in ev_metrics
-        val = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
-                                  st.get('tokens', 32), rank, world, dev, qa=qa,
-                                  candidates=st.get('candidates') if mc else None,
-                                  captions=st.get('captions') if varied else None)
+        if packed and packed.get('test'):                # the packed test split through the centre-crop path
+            from clover_amd.utils.packed_loader import packed_loaders
+            val = packed_loaders(packed, 'test', cfg.get('videos_per_gpu', 8), dev, rank, world)[0]
+        else:
+            val = SyntheticTestLoader(st.get('pairs', 64), cfg.get('videos_per_gpu', 8), st.get('frames', 8),
+                                      st.get('tokens', 32), rank, world, dev, qa=qa,
+                                      candidates=st.get('candidates') if mc else None,
+                                      captions=st.get('captions') if varied else None)
         runner.register_hook(EvalHook(val, printer=print if rank == 0 else None, **ev))
     if cfg.get('ema_hook'):                              # tools/train.py:212-220 — on EVERY rank: each keeps its own average
         from clover_amd.runner import EMA_HOOKS
